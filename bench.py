@@ -10,8 +10,13 @@ of ``--max-new-tokens`` tokens (hand-written HIP GEMM / attention / norm / rope 
 HIP-graph decode loop) -> detokenise.  Synthetic clinical notes + random-init weights
 of the named architectures (no checkpoints or datasets are reachable).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N>1: launched by torchrun, one rank per GPU, RANK/WORLD_SIZE from the env)
+
+A plain run sets up, warms up, times the K steps and prints the one JSON result line.
+``--dump-outputs DIR`` also writes what the last timed step returned to its caller (see
+``dump_outputs``); ``--full`` adds every check that takes work of its own (the sharded-
+vs-unsharded retrieval check).
 """
 from __future__ import annotations
 
@@ -74,9 +79,18 @@ def main() -> None:
     ap.add_argument("--check-retrieval", dest="check_retrieval", action="store_true", default=None,
                     help="after the timed region, check every rank's sharded top-k against an unsharded "
                          "flat search over the whole corpus (exit 3 on a mismatch); untimed.  Default: on "
-                         "whenever WORLD_SIZE > 1 (the sharded index), off on one GPU")
+                         "with --full, off otherwise")
     ap.add_argument("--no-check-retrieval", dest="check_retrieval", action="store_false")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the checks a plain run leaves out (today: the "
+                         "retrieval check, at any world size); the result line gains their records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy "
+                         "(float64): token_ids [batch, max_new_tokens] and chunk_ids [batch, k]; ranks "
+                         "above 0 append _rank<r> to the name.  Same arguments -> same inputs")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     os.environ["QA_TEMPLATE"] = a.template or os.environ.get("QA_TEMPLATE", "cache_friendly")
 
     import torch
@@ -143,6 +157,7 @@ def main() -> None:
     a0 = (eng.stats.attn_kv_blocks, eng.stats.attn_batches)
     t0 = time.perf_counter()
     step_times, stages, chunks = [], [], set()
+    ans = []
     for ans, st, lat in pipe.answer_pipelined([batch_for(a.warmup + s) for s in range(a.steps)], params):
         step_times.append(lat)   # per-batch answer latency: prepare start -> answers ready
         stages.append(st)
@@ -153,9 +168,12 @@ def main() -> None:
     sync()
     elapsed = time.perf_counter() - t0
 
-    # the driver's multi-GPU runs verify themselves: a wrong cross-shard merge on real xGMI
-    # must fail the run, not change the scaling record silently
-    do_check = a.check_retrieval if a.check_retrieval is not None else world > 1
+    if a.dump_outputs:
+        dump_outputs(Path(a.dump_outputs), ans, a.max_new_tokens, a.k, ps.rank)
+
+    # --full runs verify themselves: a wrong cross-shard merge on real xGMI must fail the
+    # run, not change the scaling record silently
+    do_check = a.check_retrieval if a.check_retrieval is not None else a.full
     retrieval = check_retrieval(pipe, batch_for(a.warmup), sync) if do_check else None
 
     t = torch.tensor([elapsed] + step_times, dtype=torch.float64, device=dev)
@@ -235,6 +253,26 @@ def main() -> None:
     comm.destroy()
     if retrieval is not None and retrieval["bad_rows_max_over_ranks"]:
         sys.exit(3)
+
+
+def dump_outputs(out_dir: Path, answers: list, max_new_tokens: int, k: int, rank: int) -> None:
+    """What the timed path handed its caller in the last timed step, as .npy arrays (float64,
+    ids are exact): ``token_ids`` [batch, max_new_tokens], the generated tokens of every
+    question, and ``chunk_ids`` [batch, k], the index rows retrieved for its prompt; rows
+    shorter than the width are padded with -1.  The answer texts and sources are functions
+    of these two.  A few hundred KB at the default batch."""
+    import numpy as np
+
+    def table(rows, width):
+        t = np.full((len(rows), max(width, max((len(r) for r in rows), default=0))), -1.0, dtype=np.float64)
+        for i, r in enumerate(rows):
+            t[i, :len(r)] = r
+        return t
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    tag = f"_rank{rank}" if rank else ""
+    np.save(out_dir / f"token_ids{tag}.npy", table([x.token_ids for x in answers], max_new_tokens))
+    np.save(out_dir / f"chunk_ids{tag}.npy", table([x.chunk_ids for x in answers], k))
 
 
 def check_retrieval(pipe, questions: list[str], sync) -> dict:

@@ -1,6 +1,8 @@
 from pathlib import Path
 
-REFERENCE = Path("/root/reference")
-REFERENCE_FAISS = REFERENCE / "semantic-indexer" / "vector_store.faiss"
-REFERENCE_META = REFERENCE / "semantic-indexer" / "metadata_store.pkl"
-REFERENCE_CSV_DIR = REFERENCE / "semantic-indexer" / "default_data"
+# the reference's shipped index files (data its indexer wrote), stored with the suite
+GOLDEN = Path(__file__).resolve().parent / "golden"
+REFERENCE_FAISS = GOLDEN / "vector_store.faiss"
+REFERENCE_META = GOLDEN / "metadata_store.pkl"
+# sizes and SHA-256 digests of the reference's prompt templates (UTF-8)
+REFERENCE_PROMPTS = GOLDEN / "reference_prompts.json"

@@ -36,7 +36,33 @@ def test_bench_single_process_cpu():
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["value"] > 0
-    assert "retrieval_check" not in d          # one GPU: no sharded index to verify
+    assert "retrieval_check" not in d          # a plain run: the checks are behind --full
+
+
+def test_bench_full_and_dump_outputs_cpu(tmp_path):
+    """--full adds the retrieval check at world size 1; --dump-outputs writes what the last
+    timed step returned, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    env = dict(os.environ, WORLD_SIZE="1")
+    got = []
+    for name, extra in (("a", ["--full"]), ("b", [])):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *ARGS, *extra,
+                            "--dump-outputs", str(tmp_path / name)], cwd=ROOT,
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _last_json(r.stdout)
+        assert KEYS <= set(d) and d["steps"] == 2 and d["ms_per_step"] > 0
+        if extra:
+            assert d["retrieval_check"] == {"rows": 3, "k": 3, "bad_rows_max_over_ranks": 0}
+        else:
+            assert "retrieval_check" not in d
+        assert sorted(p.name for p in (tmp_path / name).iterdir()) == ["chunk_ids.npy", "token_ids.npy"]
+        got.append({n: np.load(tmp_path / name / f"{n}.npy") for n in ("token_ids", "chunk_ids")})
+    a, b = got
+    assert a["token_ids"].shape == (3, 3) and a["chunk_ids"].shape == (3, 3)     # [batch, new tokens], [batch, k]
+    assert a["token_ids"].dtype == np.float64 and (a["token_ids"] >= 0).all() and (a["chunk_ids"] >= 0).all()
+    assert np.array_equal(a["token_ids"], b["token_ids"]) and np.array_equal(a["chunk_ids"], b["chunk_ids"])
 
 
 def test_bench_two_ranks_gloo_sharded_index():
@@ -45,7 +71,7 @@ def test_bench_two_ranks_gloo_sharded_index():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), str(ROOT / "bench.py"),
-           "--gpus", "2", *ARGS]            # WORLD_SIZE > 1: the retrieval check runs by default
+           "--gpus", "2", *ARGS, "--full"]  # --full: the retrieval check runs
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -63,7 +89,7 @@ def test_bench_eight_ranks_gloo_sharded_index():
     env["OMP_NUM_THREADS"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), str(ROOT / "bench.py"),
-           "--gpus", "8", *ARGS]            # the driver's exact command: self-verifying by default
+           "--gpus", "8", *ARGS, "--full"]  # the driver's command, self-verifying with --full
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)

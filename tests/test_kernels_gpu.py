@@ -621,8 +621,6 @@ def test_knn_self_query_shipped_index(native):
     from docqa_amd.index.faiss_io import read_index
     from tests.helpers import REFERENCE_FAISS
 
-    if not REFERENCE_FAISS.exists():
-        pytest.skip("reference index not mounted")
     idx = read_index(REFERENCE_FAISS)
     xb = torch.from_numpy(idx.xb).cuda()
     norms = (xb ** 2).sum(1)

@@ -6,10 +6,7 @@ from docqa_amd.index import faiss_io
 from docqa_amd.store import metadata_io
 from tests.helpers import REFERENCE_FAISS, REFERENCE_META
 
-needs_ref = pytest.mark.skipif(not REFERENCE_FAISS.exists(), reason="reference not mounted")
 
-
-@needs_ref
 def test_read_shipped_faiss_header_and_norms():
     idx = faiss_io.read_index(REFERENCE_FAISS)
     assert idx.d == 384 and idx.ntotal == 649 and idx.metric == faiss_io.METRIC_L2
@@ -17,7 +14,6 @@ def test_read_shipped_faiss_header_and_norms():
     assert norms.min() > 0.9999 and norms.max() < 1.0001
 
 
-@needs_ref
 def test_roundtrip_byte_exact(tmp_path):
     raw = REFERENCE_FAISS.read_bytes()
     idx = faiss_io.read_index(REFERENCE_FAISS)
@@ -26,7 +22,6 @@ def test_roundtrip_byte_exact(tmp_path):
     assert out.read_bytes() == raw
 
 
-@needs_ref
 def test_read_shipped_metadata_restricted():
     rows = metadata_io.read_metadata(REFERENCE_META)
     assert len(rows) == 649
@@ -35,7 +30,6 @@ def test_read_shipped_metadata_restricted():
     assert rows[0]["type"] == "knowledge_base"
 
 
-@needs_ref
 def test_metadata_roundtrip_byte_exact(tmp_path):
     rows = metadata_io.read_metadata(REFERENCE_META)
     p = tmp_path / "m.pkl"
