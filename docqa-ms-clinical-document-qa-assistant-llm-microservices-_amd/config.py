@@ -84,6 +84,9 @@ class Settings:
     embed_model: str = field(default_factory=lambda: os.getenv("EMBED_MODEL", "minilm-l6"))
     # llm-qa
     llm_model: str = field(default_factory=lambda: os.getenv("LLM_MODEL", "llama3-8b"))
+    # generator weight format: bf16 | fp8 (per-row e4m3 copies streamed by one-row decode steps,
+    # models/llama.py quantize_fp8; read by models/checkpoint.py resolve_llama)
+    llm_weights: str = field(default_factory=lambda: os.getenv("DOCQA_LLM_WEIGHTS", "bf16"))
     top_k: int = field(default_factory=lambda: env_int("TOP_K", 3))
     max_new_tokens: int = field(default_factory=lambda: env_int("MAX_NEW_TOKENS", 256))
     temperature: float = field(default_factory=lambda: float(os.getenv("TEMPERATURE", "0")))

@@ -821,6 +821,71 @@ at::Tensor gemv_xn(const at::Tensor& Pin, const at::Tensor& res_in, at::Tensor r
   return out;
 }
 
+// batch-1 GEMV over FP8 weights (dgemm.hip gemv8_kernel): q [N, K] OCP e4m3fn codes
+// (float8_e4m3fn or uint8), scale [N] fp32 powers of two; lb codes per lane per load
+static void check_fp8w(const at::Tensor& q, const at::Tensor& scale) {
+  CHECK_GPU(q); CHECK_GPU(scale); CHECK_CONTIG(q); CHECK_CONTIG(scale); CHECK_ALIGN16(q);
+  TORCH_CHECK(q.dim() == 2 && (q.scalar_type() == at::kFloat8_e4m3fn || q.scalar_type() == at::kByte),
+              "gemv8: q must be float8_e4m3fn or uint8 [N, K]");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() == q.size(0), "gemv8: scale must be fp32 [N]");
+}
+
+at::Tensor gemv8(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, int64_t splits, int64_t rows,
+                 int64_t lb, bool glu) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_ALIGN16(x);
+  check_fp8w(q, scale);
+  const int K = x.size(-1), N = q.size(0);
+  TORCH_CHECK(q.size(1) == K && x.numel() == K, "gemv8: one row, K mismatch");
+  TORCH_CHECK(splits >= 1, "gemv8: splits >= 1");
+  c10::DeviceGuard g(x.device());
+  at::Tensor out = glu ? at::empty({1, N / 2}, x.options()) : at::empty({splits, 1, N}, x.options().dtype(at::kFloat));
+  CHECK_RC(docqa_gemv8(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), glu ? out.data_ptr() : nullptr,
+                       glu ? nullptr : out.data_ptr<float>(), N, K, (int)splits, (int)rows, (int)lb, glu ? 1 : 0,
+                       nullptr, 0, nullptr, nullptr, nullptr, 0.f, stream()), "gemv8");
+  return out;
+}
+
+at::Tensor gemv8_xn(const at::Tensor& Pin, const at::Tensor& res_in, at::Tensor res_out, const at::Tensor& gamma,
+                    double eps, const at::Tensor& q, const at::Tensor& scale, int64_t splits, int64_t rows,
+                    int64_t lb, bool glu) {
+  CHECK_GPU(Pin); CHECK_CONTIG(Pin); CHECK_ALIGN16(Pin); CHECK_BF16(res_in); CHECK_BF16(res_out); CHECK_BF16(gamma);
+  CHECK_CONTIG(res_in); CHECK_CONTIG(res_out); CHECK_CONTIG(gamma);
+  CHECK_ALIGN16(res_in); CHECK_ALIGN16(res_out); CHECK_ALIGN16(gamma);
+  check_fp8w(q, scale);
+  TORCH_CHECK(Pin.scalar_type() == at::kFloat && Pin.dim() == 3 && Pin.size(1) == 1, "xn: slabs fp32 [S, 1, K]");
+  const int N = q.size(0), K = q.size(1);
+  TORCH_CHECK(Pin.size(2) == K && res_in.numel() == K && res_out.numel() == K && gamma.numel() == K,
+              "xn: one row of K");
+  TORCH_CHECK(res_in.data_ptr() != res_out.data_ptr(), "xn: res_out must be a second buffer");
+  TORCH_CHECK(splits >= 1, "gemv8_xn: splits >= 1");
+  c10::DeviceGuard g(Pin.device());
+  at::Tensor out = glu ? at::empty({1, N / 2}, res_in.options()) : at::empty({splits, 1, N}, Pin.options());
+  CHECK_RC(docqa_gemv8(nullptr, q.data_ptr(), scale.data_ptr<float>(), glu ? out.data_ptr() : nullptr,
+                       glu ? nullptr : out.data_ptr<float>(), N, K, (int)splits, (int)rows, (int)lb, glu ? 1 : 0,
+                       Pin.data_ptr<float>(), Pin.size(0), res_in.data_ptr(), res_out.data_ptr(), gamma.data_ptr(),
+                       (float)eps, stream()), "gemv8_xn");
+  return out;
+}
+
+// batch-1 LM head + greedy pick over FP8 weights (dgemm.hip gemv8_kernel EPI_ARGMAX)
+std::tuple<at::Tensor, at::Tensor> gemv8_argmax_val(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale,
+                                                    int64_t n_valid, int64_t rows, int64_t lb) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_ALIGN16(x);
+  check_fp8w(q, scale);
+  const int K = x.size(-1), N = q.size(0);
+  TORCH_CHECK(x.numel() == K && q.size(1) == K, "gemv8_argmax: one row");
+  TORCH_CHECK(rows == 16 || rows == 32, "gemv8_argmax: 16 or 32 rows per workgroup");
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({1}, x.options().dtype(at::kLong));
+  auto outv = at::empty({1}, x.options().dtype(at::kFloat));
+  auto ws_v = at::empty({N / rows + 1}, x.options().dtype(at::kFloat));
+  auto ws_i = at::empty({N / rows + 1}, x.options().dtype(at::kInt));
+  CHECK_RC(docqa_gemv8_argmax(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr<int64_t>(),
+                              outv.data_ptr<float>(), ws_v.data_ptr<float>(), ws_i.data_ptr<int>(), N, K, (int)rows,
+                              (int)lb, (int)n_valid, stream()), "gemv8_argmax");
+  return {out, outv};
+}
+
 at::Tensor dgemm(const at::Tensor& x, const at::Tensor& w, int64_t splits) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
   const int K = x.size(-1), N = w.size(0);
@@ -1352,6 +1417,10 @@ TORCH_LIBRARY(docqa, m) {
   m.def("mgemm_argmax(Tensor x, Tensor w, int n_valid, int cfg=0) -> Tensor");
   m.def("dgemm_argmax_val(Tensor x, Tensor w, int n_valid) -> (Tensor, Tensor)");
   m.def("gemv_argmax_val(Tensor x, Tensor w, int n_valid) -> (Tensor, Tensor)");
+  m.def("gemv8(Tensor x, Tensor q, Tensor scale, int splits=1, int rows=16, int lb=8, bool glu=False) -> Tensor");
+  m.def("gemv8_xn(Tensor Pin, Tensor res_in, Tensor(a!) res_out, Tensor gamma, float eps, Tensor q, Tensor scale, "
+        "int splits=1, int rows=16, int lb=8, bool glu=False) -> Tensor");
+  m.def("gemv8_argmax_val(Tensor x, Tensor q, Tensor scale, int n_valid, int rows=16, int lb=8) -> (Tensor, Tensor)");
   m.def("pgemm(Tensor x, Tensor w, int epi=0) -> Tensor");
   m.def("pgemm_partial(Tensor x, Tensor w, int splits) -> Tensor");
   m.def("mgemm_argmax_val(Tensor x, Tensor w, int n_valid, int cfg=0) -> (Tensor, Tensor)");
@@ -1439,6 +1508,9 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("fp32_gemm_nt", &fp32_gemm_nt);
   m.impl("dgemm_argmax_val", &dgemm_argmax_val);
   m.impl("gemv_argmax_val", &gemv_argmax_val);
+  m.impl("gemv8", &gemv8);
+  m.impl("gemv8_xn", &gemv8_xn);
+  m.impl("gemv8_argmax_val", &gemv8_argmax_val);
   m.impl("paged_decode_fused", &paged_decode_fused);
   m.impl("paged_decode_cascade", &paged_decode_cascade);
   m.impl("paged_decode_cascade_rope", &paged_decode_cascade_rope);

@@ -137,6 +137,14 @@ int docqa_dgemm_glu_xn(const float* Pin, int Sin, const void* res_in, void* res_
 int docqa_gemv(const void* X, const void* W, void* Y, float* P, int N, int K, int S, int R, int epi,
                const float* Pin, int Sin, const void* res_in, void* res_out, const void* gamma, float eps,
                hipStream_t s);
+// batch-1 GEMV over FP8 weights (dgemm.hip gemv8_kernel): Wq [N, K] OCP e4m3fn codes, scale [N]
+// fp32 powers of two; R rows per workgroup, LB codes per lane per load (8 | 16); otherwise as
+// docqa_gemv / docqa_gemv_argmax.  -1 (nothing launched) for a shape without an instantiation.
+int docqa_gemv8(const void* X, const void* Wq, const float* scale, void* Y, float* P, int N, int K, int S, int R,
+                int LB, int epi, const float* Pin, int Sin, const void* res_in, void* res_out, const void* gamma,
+                float eps, hipStream_t s);
+int docqa_gemv8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
+                       int* ws_i, int N, int K, int R, int LB, int n_valid, hipStream_t s);
 int docqa_embed_rmsnorm(const int* ids, const void* table, const void* w, void* h, void* x, int T, int H, int V,
                         float eps, hipStream_t s);
 int docqa_fp32_gemm_nt(const float* x, int nq, int d, const float* w, int n, float* out, hipStream_t s);

@@ -902,3 +902,245 @@ int docqa_gemv_argmax(const void* X, const void* W, int64_t* out, float* outv, f
   DOCQA_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------
+// FP8 weight stream for the batch-1 GEMV: the same register-streaming design over weights
+// stored as OCP e4m3fn codes Wq [N, K] (one byte each) with one power-of-two fp32 scale per
+// output row, W'[n, k] = Wq[n, k] * scale[n] (exactly the model's resident bf16 weights), so
+// a projection moves half the bytes.  Each lane issues all its loads at once -- its row
+// scale, the input row (bf16, unless XN builds it in LDS), then R rows x C chunks of LB = 8 or
+// 16 codes, non-temporal -- and retires them in issue order with counted vmcnt waits;
+// v_cvt_pk_f32_fp8 widens two codes per instruction, fp32 FMAs against the widened input
+// row accumulate, the 4 waves split K and meet in LDS.  The row scale multiplies the fp32 sum
+// once, before any bf16 rounding of an epilogue (exact: a power of two).
+//   * EPI_PARTIAL: fp32 slab P[slice][n], scaled;
+//   * EPI_GLU: R / 16 8-interleaved gate|up groups -> R / 2 SwiGLU outputs, bf16;
+//   * EPI_ARGMAX: R logits -> one (value, id) partial per workgroup for argmax_merge_kernel.
+// Shapes: N % R == 0, Ks = K / S with Ks % (256 LB) == 0 (C = Ks / (256 LB) chunks per lane),
+// and 1 + C LB / 8 + R C <= 63 loads per lane (the 6-bit vmcnt counter).
+namespace {
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int LB> struct Fp8Chunk { typedef u32x2 T; };
+template <> struct Fp8Chunk<16> { typedef u32x4 T; };
+
+template <int LB>
+__device__ __forceinline__ void gload_fp8_nt(typename Fp8Chunk<LB>::T& d, const void* p) {
+  if constexpr (LB == 8) asm volatile("global_load_dwordx2 %0, %1, off nt" : "=v"(d) : "v"(p) : "memory");
+  else asm volatile("global_load_dwordx4 %0, %1, off nt" : "=v"(d) : "v"(p) : "memory");
+}
+
+__device__ __forceinline__ void gload4(float& d, const void* p) {
+  asm volatile("global_load_dword %0, %1, off" : "=v"(d) : "v"(p) : "memory");
+}
+
+// at most LEFT vector-memory ops outstanding; names the registers that become valid
+template <int LEFT, typename T>
+__device__ __forceinline__ void wait_vm_reg(T& v) {
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v) : "i"(LEFT) : "memory");
+}
+
+template <int LEFT, int C, typename T>
+__device__ __forceinline__ void wait_vm_row(T (&w)[C]) {
+  if constexpr (C == 1)
+    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(w[0]) : "i"(LEFT) : "memory");
+  else if constexpr (C == 2)
+    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w[0]), "+v"(w[1]) : "i"(LEFT) : "memory");
+  else if constexpr (C == 4)
+    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "i"(LEFT) : "memory");
+  else {
+    static_assert(C == 7, "C in {1, 2, 4, 7}");
+    asm volatile("s_waitcnt vmcnt(%7)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]),
+                 "+v"(w[6]) : "i"(LEFT) : "memory");
+  }
+}
+
+template <int R, int C, int LB, int EPI, bool XN>
+__global__ __launch_bounds__(256) void gemv8_kernel(const uint16_t* __restrict__ X, const uint8_t* __restrict__ W,
+                                                    const float* __restrict__ SC, uint16_t* __restrict__ Y,
+                                                    float* __restrict__ P, int N, int K, int Ks, XNormIn xn,
+                                                    int* __restrict__ pi = nullptr, int n_valid = 0) {
+  typedef typename Fp8Chunk<LB>::T WT;
+  constexpr int XL = C * LB / 8;      // 16-byte input-row loads per lane
+  constexpr int CK = 64 * LB;         // k covered by one wave-wide chunk
+  static_assert((R & (R - 1)) == 0, "R a power of two");
+  static_assert(EPI == EPI_PARTIAL || R % 16 == 0, "GLU / ARGMAX: whole 16-row groups");
+  static_assert(R <= 64 && 1 + XL + R * C <= 63, "loads in flight per lane must fit the vmcnt counter");
+  __shared__ __attribute__((aligned(16))) uint16_t sx[XN ? kXnMaxK : 8];
+  __shared__ float red[4][R];
+  __shared__ float xred[4];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n0 = blockIdx.x * R, slice = blockIdx.y, kbeg = slice * Ks;
+  const int kw = kbeg + wave * (Ks >> 2);           // this wave's k range
+  // issue order: row scale, input row, weights (row-major) -- retired in that order
+  float sc;
+  gload4(sc, SC + n0 + (tid & (R - 1)));
+  bf16x8 xr[XL];
+  if constexpr (!XN) {
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int h = 0; h < LB / 8; ++h) gload16<0>(xr[c * (LB / 8) + h], X + kw + c * CK + lane * LB + h * 8);
+  }
+  // weight chunk (r, c) of this lane: row n0 + r, k = kw + c * CK + lane * LB
+  WT w[R][C];
+  const uint8_t* wb = W + (size_t)n0 * K + kw + lane * LB;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+#pragma unroll
+    for (int c = 0; c < C; ++c) gload_fp8_nt<LB>(w[r][c], wb + (size_t)r * K + c * CK);
+  float xf[XL][8];
+  if constexpr (XN) {
+    xnorm_prologue(xn, K, kbeg, Ks, blockIdx.x == 0 && blockIdx.y == 0, sx, xred);
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int h = 0; h < LB / 8; ++h)
+        unpack8(*reinterpret_cast<const uint4*>(sx + (kw - kbeg) + c * CK + lane * LB + h * 8), xf[c * (LB / 8) + h]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < XL; ++i) {
+      wait_vm_reg<R * C>(xr[i]);
+      unpack8(__builtin_bit_cast(uint4, xr[i]), xf[i]);
+    }
+  }
+  wait_vm_reg<R * C>(sc);
+  float acc[R];
+  static_for<0, R>([&](auto rc) {
+    constexpr int r = decltype(rc)::value;
+    // row r's chunks landed: everything issued after them is the later rows' C chunks each
+    wait_vm_row<(R - 1 - r) * C, C>(w[r]);
+    float a = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int d = 0; d < LB / 4; ++d) {
+        const float* xv = &xf[c * (LB / 8) + (d >> 1)][(d & 1) * 4];
+        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[r][c][d], false);
+        const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[r][c][d], true);
+        a = fmaf(lo[0], xv[0], a);
+        a = fmaf(lo[1], xv[1], a);
+        a = fmaf(hi[0], xv[2], a);
+        a = fmaf(hi[1], xv[3], a);
+      }
+    acc[r] = wave_sum(a);
+  });
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) red[wave][r] = acc[r];
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  // lane r < R of wave 0: output row n0 + r, scaled
+  const int rr = tid & (R - 1);
+  const float v = (red[0][rr] + red[1][rr] + red[2][rr] + red[3][rr]) * sc;
+  if constexpr (EPI == EPI_PARTIAL) {
+    if (tid < R) P[(size_t)slice * N + n0 + tid] = v;
+  } else if constexpr (EPI == EPI_ARGMAX) {
+    // the R logits (bf16-rounded, as the unfused logits) -> one (value, id) partial per
+    // workgroup at P / pi [blockIdx.x]
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    if (tid < R && n0 + tid < n_valid) {
+      bv = bf2f(f2bf(v));
+      bi = n0 + tid;
+    }
+#pragma unroll
+    for (int o = 1; o < R; o <<= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      argmax_better(bv, bi, ov, oi);
+    }
+    if (tid == 0) {
+      P[blockIdx.x] = bv;
+      pi[blockIdx.x] = bi;
+    }
+  } else {
+    // group g: gate rows 16 g .. 16 g + 7, up rows 16 g + 8 .. 16 g + 15 -> outputs 8 g .. 8 g + 7
+    const int t = tid & (R / 2 - 1), gi = (t >> 3) * 16 + (t & 7);
+    const float g = __shfl(v, gi, 64), u = __shfl(v, gi + 8, 64);
+    if (tid < R / 2) {
+      const float gv = bf2f(f2bf(g)), uv = bf2f(f2bf(u));   // as the bf16 GEMM output
+      Y[(n0 >> 1) + tid] = f2bf(silu_f(gv) * uv);
+    }
+  }
+}
+
+template <int EPI, bool XN>
+int launch_gemv8(int R, int C, int LB, dim3 grid, hipStream_t s, const uint16_t* x, const uint8_t* w, const float* sc,
+                 uint16_t* y, float* p, int N, int K, int Ks, const XNormIn& xn, int* pi = nullptr, int nv = 0) {
+#define GEMV8_CASE(RR, CC, LL)                                                                           \
+  if (R == RR && C == CC && LB == LL) {                                                                  \
+    gemv8_kernel<RR, CC, LL, EPI, XN><<<grid, 256, 0, s>>>(x, w, sc, y, p, N, K, Ks, xn, pi, nv);        \
+    return 0;                                                                                            \
+  }
+  if constexpr (EPI == EPI_PARTIAL) {
+    GEMV8_CASE(8, 1, 8) GEMV8_CASE(16, 1, 8) GEMV8_CASE(8, 2, 8) GEMV8_CASE(16, 2, 8)
+    GEMV8_CASE(8, 1, 16) GEMV8_CASE(16, 1, 16) GEMV8_CASE(32, 1, 16)
+    if constexpr (!XN) {   // K > kXnMaxK: never the in-kernel input row
+      GEMV8_CASE(4, 4, 8) GEMV8_CASE(8, 4, 8) GEMV8_CASE(4, 7, 8) GEMV8_CASE(8, 2, 16) GEMV8_CASE(16, 2, 16)
+    }
+  } else {
+    GEMV8_CASE(16, 1, 8) GEMV8_CASE(32, 1, 8) GEMV8_CASE(16, 2, 8) GEMV8_CASE(16, 1, 16) GEMV8_CASE(32, 1, 16)
+  }
+#undef GEMV8_CASE
+  return -1;
+}
+
+// shared shape rules of the FP8 GEMV entry points; C (chunks per lane) out
+bool gemv8_shape(int N, int K, int S, int R, int LB, int* C) {
+  if (N < 1 || K < 1 || S < 1 || R < 1 || (LB != 8 && LB != 16) || K % S || N % R) return false;
+  const int Ks = K / S;
+  if (Ks % (256 * LB)) return false;
+  *C = Ks / (256 * LB);
+  return true;
+}
+}  // namespace
+
+// Batch-1 GEMV over FP8 weights (see gemv8_kernel): Wq [N, K] e4m3fn codes, scale [N] fp32.
+// epi 0: fp32 slabs P [S, 1, N]; epi 1: SwiGLU Y [1, N / 2] (R % 16 == 0, S = 1).  LB: codes per
+// lane per load (8 or 16).  Pin != null: the input row from the previous projection's slabs.
+// -1 for any shape / (R, C, LB) without an instantiation: nothing is launched.
+int docqa_gemv8(const void* X, const void* Wq, const float* scale, void* Y, float* P, int N, int K, int S, int R,
+                int LB, int epi, const float* Pin, int Sin, const void* res_in, void* res_out, const void* gamma,
+                float eps, hipStream_t s) {
+  int C = 0;
+  if (!gemv8_shape(N, K, S, R, LB, &C) || !Wq || !scale || !docqa_aligned16(Wq)) return -1;
+  const int Ks = K / S;
+  const bool xnm = Pin != nullptr;
+  const XNormIn xn{Pin, Sin, (const uint16_t*)res_in, (uint16_t*)res_out, (const uint16_t*)gamma, eps};
+  if (xnm && !xn_ok(N, K, 1, R, xn)) return -1;
+  if (!xnm && (!X || !docqa_aligned16(X))) return -1;
+  if (epi == 1 ? (R % 16 || S != 1 || !Y) : !P) return -1;
+  const dim3 grid(N / R, S);
+  const uint16_t* x = (const uint16_t*)X;
+  const uint8_t* w = (const uint8_t*)Wq;
+  int rc;
+  if (epi == 1)
+    rc = xnm ? launch_gemv8<EPI_GLU, true>(R, C, LB, grid, s, x, w, scale, (uint16_t*)Y, nullptr, N, K, Ks, xn)
+             : launch_gemv8<EPI_GLU, false>(R, C, LB, grid, s, x, w, scale, (uint16_t*)Y, nullptr, N, K, Ks, xn);
+  else
+    rc = xnm ? launch_gemv8<EPI_PARTIAL, true>(R, C, LB, grid, s, x, w, scale, nullptr, P, N, K, Ks, xn)
+             : launch_gemv8<EPI_PARTIAL, false>(R, C, LB, grid, s, x, w, scale, nullptr, P, N, K, Ks, xn);
+  if (rc) return rc;
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// Batch-1 LM head + greedy pick over FP8 weights: R (16 or 32) vocabulary rows per workgroup,
+// one (value, id) partial each, merged by argmax_merge_kernel.  ws_v / ws_i: N / R entries.
+int docqa_gemv8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
+                       int* ws_i, int N, int K, int R, int LB, int n_valid, hipStream_t s) {
+  int C = 0;
+  if (!gemv8_shape(N, K, 1, R, LB, &C) || R % 16 || !X || !Wq || !scale || !out || !ws_v || !ws_i ||
+      !docqa_aligned16(X) || !docqa_aligned16(Wq) || n_valid <= 0 || n_valid > N)
+    return -1;
+  const int rc = launch_gemv8<EPI_ARGMAX, false>(R, C, LB, dim3(N / R), s, (const uint16_t*)X, (const uint8_t*)Wq,
+                                                 scale, nullptr, ws_v, N, K, K, XNormIn{}, ws_i, n_valid);
+  if (rc) return rc;
+  argmax_merge_kernel<<<1, 256, 0, s>>>(ws_v, ws_i, N / R, out, outv);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}

@@ -143,17 +143,31 @@ def resolve_llama_config(name_or_path) -> LlamaConfig:
     return LlamaConfig.preset(str(name_or_path))
 
 
+# DOCQA_LLM_WEIGHTS values -> quantize to FP8
+LLM_WEIGHTS = {"bf16": False, "bfloat16": False, "fp8": True, "fp8-e4m3": True}
+
+
 def resolve_llama(name_or_path, device="cuda", seed: int = 0) -> LlamaModel:
     """A checkpoint directory -> its weights; a preset name -> random-init weights.
     ``DOCQA_LLM_DTYPE`` (bfloat16 | float32; default bfloat16): the weight / KV dtype --
     float32 for CPU rehearsals that compare TP = N against TP = 1 token for token (bf16
     rounds each TP split's sums differently, which flips near-tied greedy picks of a
-    random-init model)."""
+    random-init model).
+    ``DOCQA_LLM_WEIGHTS`` (bf16 | fp8; default bf16): ``fp8`` quantizes the projections and the
+    LM head after loading (:meth:`LlamaModel.quantize_fp8`; TP = 1 only) -- on any dtype and
+    device, so a float32 / CPU model is the same quantized model on the reference path."""
     dtype = {"bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float32": torch.float32,
              "fp32": torch.float32}[os.environ.get("DOCQA_LLM_DTYPE", "bfloat16")]
+    weights = os.environ.get("DOCQA_LLM_WEIGHTS", "bf16").lower()
+    if weights not in LLM_WEIGHTS:
+        raise ValueError(f"DOCQA_LLM_WEIGHTS must be one of {sorted(LLM_WEIGHTS)}, not {weights!r}")
     if is_checkpoint(name_or_path):
-        return load_llama(name_or_path, device=device, dtype=dtype)
-    return LlamaModel(LlamaConfig.preset(str(name_or_path)), device=device, dtype=dtype, seed=seed)
+        model = load_llama(name_or_path, device=device, dtype=dtype)
+    else:
+        model = LlamaModel(LlamaConfig.preset(str(name_or_path)), device=device, dtype=dtype, seed=seed)
+    if LLM_WEIGHTS[weights]:
+        model.quantize_fp8()
+    return model
 
 
 # --------------------------------------------------------------------------- BERT

@@ -171,6 +171,9 @@ class LlamaModel:
         self.layers: list[dict] = []
         self._tick = None      # decode attention's last-arriver merge tickets (ops.decode_ticket)
         self._ntick = None     # fused projection + add + RMSNorm ticket word (ops.dgemm_add_rmsnorm)
+        # FP8 weight copies (quantize_fp8): per layer {name: (q, s)} and the LM head's (q, s)
+        self.fp8: list[dict] | None = None
+        self.lm_head_fp8 = None
         if init:
             self._random_init(seed)
 
@@ -280,11 +283,49 @@ class LlamaModel:
                        p + "post_attention_layernorm.weight": L["post_norm"]})
         return {k: t.detach().cpu() for k, t in sd.items()}
 
+    FP8_WEIGHTS = ("qkv", "o", "gate_up", "down")
+
+    def quantize_fp8(self) -> None:
+        """FP8 weight streaming for one-row decode steps (TP = 1): every projection and the LM
+        head get a per-row e4m3fn copy (q, s) with power-of-two scales
+        (ops.quantize_fp8_rows), and the resident weights are REPLACED by its exact image
+        W' = q * s.  Every kernel that reads W' (prefill, batched decode, mixed steps, sampled
+        logits, the CPU reference) then computes the same model the FP8 GEMV streams from half
+        the bytes, so a request sees one model whatever batch it lands in.  Embedding and
+        norms stay as they are.  The copies cost memory (about +50 % of the projections)
+        and save none.  Call after random init or load_state_dict_hf, before any decode graph
+        is captured."""
+        if self.tp != 1:
+            raise ValueError("FP8 weights need tp_size == 1: per-row scales of the row-parallel O / down shards "
+                             "would depend on the shard's K range and break the TP-invariant weights")
+        if self.fp8 is not None:
+            return
+        fp8 = []
+        for L in self.layers:
+            d = {}
+            for k in self.FP8_WEIGHTS:
+                q, s = ops.quantize_fp8_rows(L[k])
+                L[k] = ops.dequantize_fp8_rows(q, s, self.dtype)
+                d[k] = (q, s)
+            fp8.append(d)
+        q, s = ops.quantize_fp8_rows(self.lm_head)
+        self.lm_head = ops.dequantize_fp8_rows(q, s, self.dtype)
+        self.lm_head_fp8 = (q, s)
+        self.fp8 = fp8
+
+    @property
+    def weight_format(self) -> str:
+        return "fp8-e4m3" if self.fp8 is not None else "bf16"
+
     def weight_bytes(self) -> int:
         n = self.embed.numel() + self.lm_head.numel() + self.final_norm.numel()
         for L in self.layers:
             n += sum(t.numel() for t in L.values())
-        return n * self.embed.element_size()
+        n *= self.embed.element_size()
+        if self.fp8 is not None:   # the FP8 copies are held next to the bf16 image
+            for q, s in [self.lm_head_fp8] + [t for d in self.fp8 for t in d.values()]:
+                n += q.numel() * q.element_size() + s.numel() * s.element_size()
+        return n
 
     # ------------------------------------------------------------------ forward
     def forward(self, input_ids: torch.Tensor, meta: AttnMeta, kv_caches: list,
@@ -309,6 +350,11 @@ class LlamaModel:
         lin = ops.decode_linear if decode else ops.prefill_linear
         M = x.shape[0]
         plans = {}
+        # one-row decode steps of a quantize_fp8() model stream the FP8 copies where
+        # ops.gemv8_plan / gemv8_glu_ok have a kernel (w8: those projections); the rest, and
+        # every other step shape, run on the bf16 image W'
+        use8 = not meta.prefill and self.fp8 is not None and x.is_cuda and M == 1
+        w8: dict = {}
         # a short prefill (<= ops.MID_M_MAX prompt tokens: batch-1 serving) has the decode
         # step's shape -- too few rows for the 256 x 256 prefill GEMM's tiles -- so it takes
         # the same split-K projection plans and fused consumers (RoPE + KV write, add + norm)
@@ -329,6 +375,12 @@ class LlamaModel:
                                    and ops.fused_decode_ok(kv_caches[0][0], meta.block_tables))))
             b16 = {"qkv": s16 and qkv_rope, "o": s16, "down": s16}
             for k in ("qkv", "o", "down"):
+                S8, R8 = ops.gemv8_plan(M, *L0[k].shape) if use8 else (0, 0)
+                if S8:
+                    # one row, FP8 weights: the same GEMV over the (q, s) copy, half the bytes
+                    w8[k] = (S8, R8)
+                    plans[k] = (S8, lambda a, w, S=S8, R=R8: ops.gemv8_partial(a, w[0], w[1], S, R))
+                    continue
                 Sg, R = ops.gemv_plan(M, *L0[k].shape) if x.is_cuda else (0, 0)
                 if Sg:
                     # one row: the register-streaming GEMV (no LDS ring) -- QKV / O
@@ -352,7 +404,10 @@ class LlamaModel:
                 if Sd:
                     plans["down"] = (Sd, lambda a, w, S=Sd: ops.pgemm_partial(a, w, S))
             Sg, cg = ops.mid_plan(M, *L0["gate_up"].shape, glu=True)
-            if decode and x.is_cuda and ops.gemv_glu_ok(M, *L0["gate_up"].shape):
+            if use8 and ops.gemv8_glu_ok(M, *L0["gate_up"].shape):
+                w8["gate_up"] = (1, 0)
+                glu = lambda a, w: ops.gemv8_glu(a, w[0], w[1])  # noqa: E731
+            elif decode and x.is_cuda and ops.gemv_glu_ok(M, *L0["gate_up"].shape):
                 glu = ops.gemv_glu        # one row: the register-streaming GEMV with SwiGLU
             elif small and (ops.pgemm_ok(M, *L0["gate_up"].shape)
                           or ops.prefill_split_plan(M, *L0["gate_up"].shape, glu=True)):
@@ -388,7 +443,7 @@ class LlamaModel:
         # batch 1 (<= ops.NORM_FUSE_ROWS rows, TP = 1): O / down with the residual add + RMSNorm
         # in the projection's own last workgroup -- no add_rmsnorm_splitk launch
         nf = {}
-        if decode and self.tp == 1 and self.layers and x.is_cuda:
+        if decode and self.tp == 1 and self.layers and x.is_cuda and not w8:
             L0 = self.layers[0]
             for k in ("o", "down"):
                 S = ops.dgemm_norm_plan(M, *L0[k].shape)
@@ -415,10 +470,15 @@ class LlamaModel:
         pd = None   # XN: the previous layer's down-projection slabs
         for i, L in enumerate(self.layers):
             kc, vc = kv_caches[i]
+            if w8:   # this layer's weights: the FP8 (q, s) pairs where the plan streams them
+                L = {**L, **{k: self.fp8[i][k] for k in w8}}
             if sq:
                 if xn and pd is not None:
-                    Sg, R = ops.gemv_plan(M, *L["qkv"].shape)
-                    if Sg == sq:
+                    Sg, R = ops.gemv_plan(M, *self.layers[i]["qkv"].shape)
+                    if "qkv" in w8:
+                        qkv_slabs = ops.gemv8_partial_xn(pd, residual, res2, L["in_norm"], eps, *L["qkv"], sq,
+                                                         w8["qkv"][1])
+                    elif Sg == sq:
                         qkv_slabs = ops.gemv_partial_xn(pd, residual, res2, L["in_norm"], eps, L["qkv"], sq, R)
                     else:
                         qkv_slabs = ops.dgemm_partial_xn(pd, residual, res2, L["in_norm"], eps, L["qkv"], sq)
@@ -508,7 +568,9 @@ class LlamaModel:
                                      meta.max_context, self.scale, meta.seq_order)
             nxt = self.layers[i + 1]["in_norm"] if i + 1 < nl else self.final_norm
             if xn:
-                if ops.gemv_glu_ok(M, *L["gate_up"].shape):
+                if "gate_up" in w8:
+                    g = ops.gemv8_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, *L["gate_up"])
+                elif ops.gemv_glu_ok(M, *L["gate_up"].shape):
                     g = ops.gemv_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, L["gate_up"])
                 else:
                     g = ops.dgemm_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, L["gate_up"])
@@ -619,7 +681,7 @@ class LlamaModel:
                                                    and ops.lm_head_argmax_shape_ok(N, K))
         if self.tp == 1:
             if fused:
-                return ops.lm_head_argmax(x, self.lm_head, self.cfg.vocab_size)
+                return ops.lm_head_argmax(x, self.lm_head, self.cfg.vocab_size, fp8=self.lm_head_fp8)
             return self.greedy(ops.lm_head_logits(x, self.lm_head))
         if fused and self.vocab_valid > 0:
             ids, vals = ops.lm_head_argmax(x, self.lm_head, self.vocab_valid, with_values=True)

@@ -540,12 +540,18 @@ _LM_CFG = int(os.environ.get("DOCQA_LM_HEAD_CFG", "6"))
 _GEMV_LM = os.environ.get("DOCQA_GEMV_LM", "1") != "0"
 
 
-def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False):
+def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False, fp8=None):
     """Greedy token ids argmax(bf16(x @ w[:n_valid]^T)) with the LM-head GEMM and the argmax
     fused (mgemm.hip EPI_ARGMAX): the [M, vocab] logits never reach HBM.  ``with_values``:
-    (ids, picked logit fp32) -- a vocab-parallel shard's candidates for comm.tp_argmax."""
+    (ids, picked logit fp32) -- a vocab-parallel shard's candidates for comm.tp_argmax.
+    ``fp8``: the (q, s) FP8 copy of ``w`` (:func:`quantize_fp8_rows`, ``w`` its exact image) --
+    a one-row step then streams the codes (dgemm.hip gemv8_kernel EPI_ARGMAX)."""
     if _gpu(x):
         N, K = w.shape
+        if fp8 is not None and n_valid > 0 and gemv8_argmax_ok(x.numel() // K, N, K):
+            R, lb = _GEMV8_EPI[K]
+            ids, vals = _native().gemv8_argmax_val(x.contiguous(), fp8[0], fp8[1], int(n_valid), R, lb)
+            return (ids, vals) if with_values else ids
         if (_GEMV_LM and x.numel() == K and N % 16 == 0 and K % 2048 == 0 and K // 2048 <= 2
                 and n_valid > 0):
             # one row: the register-streaming GEMV with the argmax in its epilogue
@@ -700,6 +706,93 @@ def gemv_glu_xn(Pin, res_in, res_out, gamma, eps: float, w_il):
     if _gpu(Pin):
         return _native().gemv_xn(Pin, res_in, res_out, gamma, float(eps), w_il, 1, 16, True)
     return dgemm_glu_xn(Pin, res_in, res_out, gamma, eps, w_il)
+
+
+# ----------------------------------------------------------------------------- FP8 weights
+# Batch-1 GEMV over FP8 weights (dgemm.hip gemv8_kernel): per output row OCP e4m3fn codes q
+# and a power-of-two scale s, W' = q * s exactly the model's resident bf16 weights
+# (LlamaModel.quantize_fp8), so a one-row step streams half the bytes and computes the same
+# products as every other kernel does from W'.
+quantize_fp8_rows, dequantize_fp8_rows = ref.quantize_fp8_rows, ref.dequantize_fp8_rows
+
+_GEMV8 = os.environ.get("DOCQA_GEMV8", "1") != "0"
+# K -> (split-K count, weight rows per workgroup, codes per lane per load) of the split-K slab
+# projections, and K -> (rows, codes per load) of the SwiGLU / LM-head argmax epilogues.  Every
+# entry names an instantiation of gemv8_kernel (GEMV8_CASES); shapes that are absent keep the
+# bf16 GEMV on W'.  benchmarks/bench_gemv_fp8.py times each entry against the bf16 plan
+# (profiles/fp8_gemv_probe.log: QKV 9.9 vs 12.2 us, O 6.9 vs 7.9, gate|up 25.3 vs 39.3, down 13.1
+# vs 20.0, LM head 89.2 vs 159.0 at Llama-3-8B -- every shape faster, so every one is listed).
+_GEMV8_PLAN = {2048: (1, 8, 8), 4096: (1, 8, 16), 8192: (1, 8, 16), 14336: (1, 4, 8)}
+_GEMV8_EPI = {2048: (16, 8), 4096: (16, 16)}
+# (rows, chunks per lane, codes per load) instantiated for slabs; XN: also with the in-kernel
+# input row (K <= 4096); EPI: the SwiGLU / argmax epilogues
+GEMV8_CASES = [(8, 1, 8), (16, 1, 8), (8, 2, 8), (16, 2, 8), (8, 1, 16), (16, 1, 16), (32, 1, 16),
+               (4, 4, 8), (8, 4, 8), (4, 7, 8), (8, 2, 16), (16, 2, 16)]
+GEMV8_XN_CASES = GEMV8_CASES[:7]
+GEMV8_EPI_CASES = [(16, 1, 8), (32, 1, 8), (16, 2, 8), (16, 1, 16), (32, 1, 16)]
+
+
+def gemv8_plan(M: int, N: int, K: int) -> tuple[int, int]:
+    """(split-K count, weight rows per workgroup) of the FP8-weight GEMV for a one-row
+    projection; (0, 0) where the kernel has no instantiation or does not beat the bf16 GEMV
+    (the caller then streams the bf16 image W').  DOCQA_GEMV8=0 disables."""
+    S, R, lb = _GEMV8_PLAN.get(K, (0, 0, 0))
+    if not _GEMV8 or M != 1 or not S or N % R or (K // S) % (256 * lb):
+        return 0, 0
+    if (R, K // S // (256 * lb), lb) not in GEMV8_CASES:
+        return 0, 0
+    return S, R
+
+
+def gemv8_lb(K: int, splits: int = 1) -> int:
+    """Codes per lane per load (8 | 16) the plan tables use at this K (8 where none)."""
+    if K in _GEMV8_PLAN and _GEMV8_PLAN[K][0] == splits:
+        return _GEMV8_PLAN[K][2]
+    return 8
+
+
+def gemv8_glu_ok(M: int, N: int, K: int) -> bool:
+    """The batch-1 gate|up projection with SwiGLU on the FP8-weight GEMV."""
+    R, lb = _GEMV8_EPI.get(K, (0, 0))
+    return bool(_GEMV8 and M == 1 and R and N % R == 0 and (R, K // (256 * lb), lb) in GEMV8_EPI_CASES)
+
+
+def gemv8_argmax_ok(M: int, N: int, K: int) -> bool:
+    """The batch-1 LM head + greedy pick on the FP8-weight GEMV."""
+    return gemv8_glu_ok(M, N, K)
+
+
+def gemv8_partial(x, q, s, splits: int, rows: int, lb: int = 0):
+    """fp32 slabs [S, 1, N] of one row x @ (q * s)^T on the FP8-weight GEMV (:func:`gemv8_plan`)."""
+    if _gpu(x):
+        return _native().gemv8(x.contiguous(), q, s, int(splits), int(rows), int(lb) or gemv8_lb(q.shape[1], splits),
+                               False)
+    return gemv_partial(x, dequantize_fp8_rows(q, s, x.dtype), splits, rows)
+
+
+def gemv8_partial_xn(Pin, res_in, res_out, gamma, eps: float, q, s, splits: int, rows: int, lb: int = 0):
+    """:func:`gemv_partial_xn` (input row built in-kernel) over FP8 weights."""
+    if _gpu(Pin):
+        return _native().gemv8_xn(Pin, res_in, res_out, gamma, float(eps), q, s, int(splits), int(rows),
+                                  int(lb) or gemv8_lb(q.shape[1], splits), False)
+    return gemv_partial_xn(Pin, res_in, res_out, gamma, eps, dequantize_fp8_rows(q, s, res_in.dtype), splits, rows)
+
+
+def gemv8_glu(x, q, s, rows: int = 0, lb: int = 0):
+    """silu(x Wg^T) * (x Wu^T) for one row over FP8 8-interleaved gate|up weights."""
+    if _gpu(x):
+        R, l = _GEMV8_EPI.get(q.shape[1], (16, 8))
+        return _native().gemv8(x.contiguous(), q, s, 1, int(rows) or R, int(lb) or l, True)
+    return gemv_glu(x, dequantize_fp8_rows(q, s, x.dtype))
+
+
+def gemv8_glu_xn(Pin, res_in, res_out, gamma, eps: float, q, s, rows: int = 0, lb: int = 0):
+    """:func:`gemv_glu_xn` (input row built in-kernel, SwiGLU epilogue) over FP8 weights."""
+    if _gpu(Pin):
+        R, l = _GEMV8_EPI.get(q.shape[1], (16, 8))
+        return _native().gemv8_xn(Pin, res_in, res_out, gamma, float(eps), q, s, 1, int(rows) or R, int(lb) or l,
+                                  True)
+    return gemv_glu_xn(Pin, res_in, res_out, gamma, eps, dequantize_fp8_rows(q, s, res_in.dtype))
 
 
 NORM_FUSE_ROWS = 4

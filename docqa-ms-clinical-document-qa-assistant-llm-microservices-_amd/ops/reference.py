@@ -120,6 +120,40 @@ def glu_split(gu):
     return v[:, 0].reshape(-1, gu.shape[-1]), v[:, 1].reshape(-1, gu.shape[-1])
 
 
+FP8_MAX = 448.0          # largest finite OCP e4m3fn value
+# amax / scale lands in (232, 464]: 464 is the midpoint between 448 and the next (absent) code,
+# so everything up to it rounds to 448 anyway, and the top code is never below 240 -- which is
+# what makes quantizing the dequantized image again give the same (q, s).  (With 448 as the
+# bound a row whose amax / scale falls in (224, 232] rounds to a top code of 224 and would
+# re-quantize to (2 q, s / 2).)  An amax of exactly 448 * 2^e gets scale 2^e either way.
+_FP8_BOUND = 464.0
+_FP8_MIN_EXP = -100      # q * s stays a normal bf16 / fp32 number down to the smallest code
+
+
+def quantize_fp8_rows(w):
+    """Per-row FP8 weight format: ``w`` [N, K] -> (q [N, K] float8_e4m3fn, s [N] fp32) with
+    ``s[n]`` an exact power of two, ``2^ceil(log2(amax_n / 464))`` (1 for an all-zero row), and
+    ``q = rne(w / s)`` saturated to +-448 -- the NaN codes 0x7f / 0xff are never produced.
+    ``q * s`` has a 3-bit mantissa, so it is exact in bf16 (:func:`dequantize_fp8_rows`)."""
+    wf = w.detach().float()
+    amax = wf.abs().amax(dim=1)
+    # amax = m * 2^e, m in [0.5, 1); 464 = 0.90625 * 2^9 -- compared exactly, no division
+    m, e = torch.frexp(amax)
+    ex = torch.where(m > _FP8_BOUND / 512.0, e - 8, e - 9).clamp_(min=_FP8_MIN_EXP)
+    s = torch.ldexp(torch.ones_like(amax), ex)
+    s = torch.where(amax > 0, s, torch.ones_like(s))
+    q = (wf / s[:, None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q, s
+
+
+def dequantize_fp8_rows(q, s, dtype=torch.bfloat16):
+    """``q * s`` of :func:`quantize_fp8_rows` in ``dtype`` (exact in bf16 and fp32); ``q`` as
+    float8_e4m3fn or its uint8 codes."""
+    if q.dtype == torch.uint8:
+        q = q.view(torch.float8_e4m3fn)
+    return (q.float() * s.float()[:, None]).to(dtype)
+
+
 def bias_act(x, bias, residual, gelu):
     y = x.float()
     if residual is not None:

@@ -197,6 +197,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--tiny", action="store_true", help="tiny random models (CPU demo / CI)")
     ap.add_argument("--llm", default="llama3-8b")
+    ap.add_argument("--llm-weights", choices=("bf16", "fp8"), default=None,
+                    help="generator weight format (DOCQA_LLM_WEIGHTS): fp8 streams per-row e4m3 weights in "
+                         "single-question decode steps (TP = 1)")
     ap.add_argument("--embed", default="minilm-l6")
     ap.add_argument("--real-synthese", action="store_true")
     ap.add_argument("--services", default="", help="comma list of ingest,deid,indexer,qa,synthese,ui (default all)")
@@ -219,6 +222,10 @@ def main() -> None:
     a = build_parser().parse_args()
     import os
     import sys
+
+    if a.llm_weights is not None:
+        # before any worker / supervised child is spawned: they inherit the environment
+        os.environ["DOCQA_LLM_WEIGHTS"] = a.llm_weights
 
     # The HTTP front end (uvicorn thread), the QA prep thread and the engine's scheduler
     # thread share one GIL; at CPython's 5 ms switch interval each request's few GIL hand-

@@ -189,7 +189,8 @@ def register(app: FastAPI, settings, metrics) -> None:
                            "size": int(m.weight_bytes()), "digest": "",
                            "details": {"format": "safetensors", "family": "llama", "families": ["llama"],
                                        "parameter_size": f"{m.cfg.num_params() / 1e9:.1f}B",
-                                       "quantization_level": "BF16"}})
+                                       "quantization_level": ("F8_E4M3" if getattr(m, "weight_format", "bf16")
+                                                              == "fp8-e4m3" else "BF16")}})
         return {"models": models}
 
     @app.get("/api/version")
