@@ -823,11 +823,14 @@ at::Tensor gemv_xn(const at::Tensor& Pin, const at::Tensor& res_in, at::Tensor r
 
 // batch-1 GEMV over FP8 weights (dgemm.hip gemv8_kernel): q [N, K] OCP e4m3fn codes
 // (float8_e4m3fn or uint8), scale [N] fp32 powers of two; lb codes per lane per load
-static void check_fp8w(const at::Tensor& q, const at::Tensor& scale) {
-  CHECK_GPU(q); CHECK_GPU(scale); CHECK_CONTIG(q); CHECK_CONTIG(scale); CHECK_ALIGN16(q);
-  TORCH_CHECK(q.dim() == 2 && (q.scalar_type() == at::kFloat8_e4m3fn || q.scalar_type() == at::kByte),
-              "gemv8: q must be float8_e4m3fn or uint8 [N, K]");
-  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() == q.size(0), "gemv8: scale must be fp32 [N]");
+static void check_fp8w(const at::Tensor& q, const at::Tensor& scale, const char* op = "gemv8") {
+  TORCH_CHECK(q.is_cuda() && scale.is_cuda(), op, ": q and scale must be GPU tensors");
+  TORCH_CHECK(q.is_contiguous() && scale.is_contiguous(), op, ": q and scale must be contiguous");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15u) == 0, op,
+              ": q must be 16-byte aligned (storage offset a multiple of 16 bytes)");
+  TORCH_CHECK(q.dim() == 2 && (q.scalar_type() == at::kFloat8_e4m3fn || q.scalar_type() == at::kByte), op,
+              ": q must be float8_e4m3fn or uint8 [N, K]");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.numel() == q.size(0), op, ": scale must be fp32 [N]");
 }
 
 at::Tensor gemv8(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, int64_t splits, int64_t rows,
@@ -883,6 +886,56 @@ std::tuple<at::Tensor, at::Tensor> gemv8_argmax_val(const at::Tensor& x, const a
   CHECK_RC(docqa_gemv8_argmax(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr<int64_t>(),
                               outv.data_ptr<float>(), ws_v.data_ptr<float>(), ws_i.data_ptr<int>(), N, K, (int)rows,
                               (int)lb, (int)n_valid, stream()), "gemv8_argmax");
+  return {out, outv};
+}
+
+// 2..32-row decode projections over FP8 weights (dgemm.hip dgemm8_kernel); a shape without an
+// instantiation launches nothing and raises, naming the op
+static int dgemm8_rows(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, const char* op) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(), op,
+              ": x must be a contiguous bfloat16 GPU tensor");
+  check_fp8w(q, scale, op);
+  const int64_t K = x.size(-1);
+  TORCH_CHECK(q.size(1) == K, op, ": K mismatch");
+  const int64_t M = x.numel() / K;
+  TORCH_CHECK(M <= 32, op, ": at most 32 rows, got ", M);
+  return (int)M;
+}
+
+at::Tensor dgemm8_partial(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, int64_t splits,
+                          int64_t tile_rows) {
+  const int M = dgemm8_rows(x, q, scale, "dgemm8_partial");
+  const int N = q.size(0), K = q.size(1);
+  TORCH_CHECK(splits >= 1, "dgemm8_partial: splits >= 1");
+  c10::DeviceGuard g(x.device());
+  auto part = at::empty({splits, M, N}, x.options().dtype(at::kFloat));
+  CHECK_RC(docqa_dgemm8_partial(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), part.data_ptr<float>(), M, N, K,
+                                (int)splits, (int)tile_rows, stream()), "dgemm8_partial");
+  return part;
+}
+
+at::Tensor dgemm8_glu(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale) {
+  const int M = dgemm8_rows(x, q, scale, "dgemm8_glu");
+  const int N = q.size(0), K = q.size(1);
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({M, N / 2}, x.options());
+  CHECK_RC(docqa_dgemm8_glu(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), M, N, K, stream()),
+           "dgemm8_glu");
+  return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> dgemm8_argmax_val(const at::Tensor& x, const at::Tensor& q,
+                                                     const at::Tensor& scale, int64_t n_valid) {
+  const int M = dgemm8_rows(x, q, scale, "dgemm8_argmax_val");
+  const int N = q.size(0), K = q.size(1);
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({M}, x.options().dtype(at::kLong));
+  auto outv = at::empty({M}, x.options().dtype(at::kFloat));
+  auto ws_v = at::empty({M, N / 64}, x.options().dtype(at::kFloat));
+  auto ws_i = at::empty({M, N / 64}, x.options().dtype(at::kInt));
+  CHECK_RC(docqa_dgemm8_argmax(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr<int64_t>(),
+                               outv.data_ptr<float>(), ws_v.data_ptr<float>(), ws_i.data_ptr<int>(), M, N, K,
+                               (int)n_valid, stream()), "dgemm8_argmax_val");
   return {out, outv};
 }
 
@@ -1421,6 +1474,9 @@ TORCH_LIBRARY(docqa, m) {
   m.def("gemv8_xn(Tensor Pin, Tensor res_in, Tensor(a!) res_out, Tensor gamma, float eps, Tensor q, Tensor scale, "
         "int splits=1, int rows=16, int lb=8, bool glu=False) -> Tensor");
   m.def("gemv8_argmax_val(Tensor x, Tensor q, Tensor scale, int n_valid, int rows=16, int lb=8) -> (Tensor, Tensor)");
+  m.def("dgemm8_partial(Tensor x, Tensor q, Tensor scale, int splits, int tile_rows=64) -> Tensor");
+  m.def("dgemm8_glu(Tensor x, Tensor q, Tensor scale) -> Tensor");
+  m.def("dgemm8_argmax_val(Tensor x, Tensor q, Tensor scale, int n_valid) -> (Tensor, Tensor)");
   m.def("pgemm(Tensor x, Tensor w, int epi=0) -> Tensor");
   m.def("pgemm_partial(Tensor x, Tensor w, int splits) -> Tensor");
   m.def("mgemm_argmax_val(Tensor x, Tensor w, int n_valid, int cfg=0) -> (Tensor, Tensor)");
@@ -1511,6 +1567,9 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("gemv8", &gemv8);
   m.impl("gemv8_xn", &gemv8_xn);
   m.impl("gemv8_argmax_val", &gemv8_argmax_val);
+  m.impl("dgemm8_partial", &dgemm8_partial);
+  m.impl("dgemm8_glu", &dgemm8_glu);
+  m.impl("dgemm8_argmax_val", &dgemm8_argmax_val);
   m.impl("paged_decode_fused", &paged_decode_fused);
   m.impl("paged_decode_cascade", &paged_decode_cascade);
   m.impl("paged_decode_cascade_rope", &paged_decode_cascade_rope);

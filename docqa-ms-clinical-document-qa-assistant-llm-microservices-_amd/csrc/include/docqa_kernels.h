@@ -145,6 +145,15 @@ int docqa_gemv8(const void* X, const void* Wq, const float* scale, void* Y, floa
                 float eps, hipStream_t s);
 int docqa_gemv8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
                        int* ws_i, int N, int K, int R, int LB, int n_valid, hipStream_t s);
+// 2..32-row decode projections over FP8 weights (dgemm.hip dgemm8_kernel: the LDS-DMA ring over
+// the codes, K slices of whole 1024-deep ring turns): fp32 slabs P [S, M, N] (tile_rows 64),
+// SwiGLU Y [M, N / 2], LM head + greedy pick (ws_v / ws_i: [M, N / 64]).  -1 (nothing launched)
+// for a shape without an instantiation.
+int docqa_dgemm8_partial(const void* X, const void* Wq, const float* scale, float* P, int M, int N, int K, int S,
+                         int tile_rows, hipStream_t s);
+int docqa_dgemm8_glu(const void* X, const void* Wq, const float* scale, void* Y, int M, int N, int K, hipStream_t s);
+int docqa_dgemm8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
+                        int* ws_i, int M, int N, int K, int n_valid, hipStream_t s);
 int docqa_embed_rmsnorm(const int* ids, const void* table, const void* w, void* h, void* x, int T, int H, int V,
                         float eps, hipStream_t s);
 int docqa_fp32_gemm_nt(const float* x, int nq, int d, const float* w, int n, float* out, hipStream_t s);

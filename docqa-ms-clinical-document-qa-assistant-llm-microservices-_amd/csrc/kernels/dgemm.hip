@@ -1144,3 +1144,300 @@ int docqa_gemv8_argmax(const void* X, const void* Wq, const float* scale, int64_
   DOCQA_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------
+// FP8 weight stream for decode steps of 2..32 rows: dgemm_kernel's ring pipeline (256 threads,
+// workgroup = NT x 16 weight rows x all M rows x one K slice, X fragments straight to VGPRs
+// one k-block ahead, counted vmcnt waits, ring_barrier, XCD-aware slice remap,
+// v_mfma_f32_16x16x32_bf16) over the e4m3fn codes Wq [N, K] + scale [N] of gemv8_kernel.
+//   * Ring depth: bytes in flight per CU are what the design is about, so a stage keeps the
+//     bf16 kernel's BYTES, not its k-depth: 256 codes (256 B) per weight row = twice the k per
+//     stage, 4 slots, the same NT LDS-DMA wave-instructions (glds16<true>, 16 B per lane, nt)
+//     per wave per stage and therefore the same issue order and vmcnt counts.  K granule: one
+//     ring turn = 4 x 256 = 1024 (Ks % 1024 == 0).
+//   * LDS layout: stage = [NT 16][256 B], i.e. 16 chunks of 16 B per row -- byte for byte the
+//     bf16 stage, so the bf16 kernel's source swizzle carries over with chunks counted in bytes:
+//     chunk c of row r lands at chunk position c ^ (r & 15).  The B fragment of k-step ks (32
+//     codes) for lane (fr = lane & 15, fq = lane >> 4) is the 8 codes k = 32 ks + 8 fq .. + 7 of
+//     row 16 nt + fr: chunk c = 2 ks + (fq >> 1), half (fq & 1), one ds_read_b64 at
+//       row * 256 + ((c ^ fr) << 4) + (fq & 1) * 8.
+//     ds_read_b64 is served in two 32-lane groups {0..31}, {32..63}, bank = (addr / 4) % 64
+//     (MI355X_MICROARCH.md, LDS): a group is conflict-free iff its 32 lanes hit 32 distinct 8-B
+//     slots of the 256-B bank row.  Inside a group fq >> 1 is constant, so c is one value, and
+//     row * 256 == 0 (mod 256): the slot is ((c ^ fr) << 1) + (fq & 1); fr = 0..15 makes c ^ fr
+//     a permutation of the 16 chunk positions and fq & 1 picks the half -- 32 distinct slots.
+//   * B fragment: v_cvt_scalef32_pk_bf16_fp8 (scale 1.0) widens two codes per instruction,
+//     four per fragment; exact (every e4m3fn value is a bf16 value; quantize_fp8_rows
+//     saturates, so no NaN codes).
+//   * Accumulators fp32; the row scale (the C/D column = weight row: one value per lane per
+//     n-tile) multiplies them once after the k loop, before the k-group sum and any bf16
+//     rounding (exact: a power of two).
+//   * MT = 1 (2..16 rows, the four waves split k) and MT = 2 (17..32 rows, two k-groups).  At
+//     33+ rows every wave would widen every fragment (4x redundant VALU work per byte), and the
+//     bf16 kernel there is no longer bound by weight bytes alone: those rows stay on W'.
+//   * Epilogues: EPI_PARTIAL / EPI_GLU / EPI_ARGMAX as dgemm_kernel's k-group (KW > 1) paths.
+namespace {
+constexpr int BK8 = 256;                  // codes (= bytes) per weight row per stage
+constexpr int KSTEPS8 = BK8 / 32;         // 16x16x32 k-steps per stage
+
+__device__ __forceinline__ int w8_off(int row, int ch, int half) {   // byte offset in a stage
+  return row * BK8 + ((ch ^ (row & 15)) << 4) + half * 8;
+}
+
+// 8 e4m3fn codes -> the bf16x8 B fragment
+__device__ __forceinline__ bf16x8 widen8(u32x2 c) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], 1.0f, true);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, false);
+  const bf16x2 e = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], 1.0f, true);
+  return bf16x8{a[0], a[1], b[0], b[1], d[0], d[1], e[0], e[1]};
+}
+
+template <int EPI, int MT, int NT>
+__global__ __launch_bounds__(256) void dgemm8_kernel(const uint16_t* __restrict__ X, const uint8_t* __restrict__ W,
+                                                     const float* __restrict__ SC, uint16_t* __restrict__ Y,
+                                                     float* __restrict__ P, int M, int N, int K, int Ks,
+                                                     int xcd_remap, float* __restrict__ pv = nullptr,
+                                                     int* __restrict__ pi = nullptr, int n_valid = 0) {
+  static_assert(MT == 1 || MT == 2, "2..16 rows (MT = 1) or 17..32 rows (MT = 2)");
+  static_assert(EPI == EPI_PARTIAL || EPI == EPI_GLU || EPI == EPI_ARGMAX, "slabs, SwiGLU or argmax");
+  constexpr int NSR = NS;                        // ring slots
+  constexpr int KW = 4 / MT, SPW = KSTEPS8 / KW; // k-groups; k-steps (= X fragments) per wave per stage
+  constexpr int VW = 2 * NT + SPW;               // vector-memory ops in flight at the top of a step
+  constexpr int STAGE = NT * 16 * BK8;           // bytes of one W stage (NT x 4 KB)
+  __shared__ __attribute__((aligned(16))) uint8_t sw[NSR * STAGE];   // W ring
+  int tile = blockIdx.x, slice = blockIdx.y;
+  if (xcd_remap) {   // XCD x only runs slice x % S (see dgemm_kernel)
+    const int S = gridDim.y;
+    const int L = blockIdx.x + blockIdx.y * gridDim.x;
+    const int xcd = L & 7, j = L >> 3;
+    slice = xcd % S;
+    tile = j * (8 / S) + xcd / S;
+  }
+  const int n0 = tile * NT * 16;
+  const int kbeg = slice * Ks;
+  const int nkb = Ks / BK8;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const int mt = wave % MT, kg = wave / MT;
+  // this lane's row scales, first in the queue: retired by the first counted wait
+  float sc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) gload4(sc[i], SC + n0 + i * 16 + fr);
+  const uint16_t* xrow = X + (size_t)min(mt * 16 + fr, M - 1) * K + kbeg + kg * SPW * 32 + fq * 8;
+  const uint32_t ring = lds_u32(sw);
+
+  f32x4 acc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // W stage j -> ring slot j % NSR: 4 NT wave-instructions of 64 lanes x 16 B (4 rows each), NT
+  // per wave, source XOR-swizzled; clamped past the last stage (see dgemm_kernel)
+  const uint8_t* wsrc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int p = (i * 4 + wave) * 64 + lane;
+    const int r = p >> 4;
+    wsrc[i] = W + (size_t)(n0 + r) * K + kbeg + (((p & 15) ^ (r & 15)) << 4);
+  }
+  auto stage_w = [&](int j) {
+    const int koff = min(j, nkb - 1) * BK8;
+    const uint32_t dst = ring + (uint32_t)((j % NSR) * STAGE);
+#pragma unroll
+    for (int i = 0; i < NT; ++i) glds16<true>(wsrc[i] + koff, dst + (uint32_t)((i * 4 + wave) * 1024));
+  };
+  auto load_x = [&](bf16x8 (&x)[SPW], int j) {
+    const uint16_t* src = xrow + min(j, nkb - 1) * BK8;
+    gload16<0>(x[0], src);
+    gload16<64>(x[1], src);
+    if constexpr (SPW > 2) { gload16<128>(x[2], src); gload16<192>(x[3], src); }
+  };
+  // n-tile byte offsets, opaque to hipcc: with constant distances it merges the reads of two
+  // n-tiles into ds_read2st64_b64, which is banked mod 32 in 16-lane groups -- there this
+  // layout is 2-way conflicted, at half the bytes per clock of ds_read_b64
+  int ntoff[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    ntoff[nt] = nt * 16 * BK8;
+    asm volatile("" : "+v"(ntoff[nt]));
+  }
+  auto mma = [&](const bf16x8 (&x)[SPW], int j) {
+    const uint8_t* src = sw + (j % NSR) * STAGE;
+#pragma unroll
+    for (int s = 0; s < SPW; ++s) {
+      const int ch = (kg * SPW + s) * 2 + (fq >> 1);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const u32x2 c = *reinterpret_cast<const u32x2*>(src + ntoff[nt] + w8_off(fr, ch, fq & 1));
+        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[s], widen8(c), acc[nt], 0, 0, 0);
+      }
+    }
+  };
+  // issue order and counted waits: dgemm_kernel's XA = 2 schedule (W0 X0 W1 X1 W2 | step i:
+  // X(i+2) W(i+3)); nkb % 4 == 0
+  bf16x8 x0[SPW], x1[SPW], x2[SPW], x3[SPW];
+  // the row scales are the oldest loads in the queue: every counted wait has retired them, and
+  // naming their registers right there (no instruction) keeps anything that reads or moves them
+  // below the first wait
+  auto name_sc = [&] {
+#pragma unroll
+    for (int i = 0; i < NT; ++i) asm volatile("" : "+v"(sc[i]));
+  };
+#define RING_STEP8(I, XC, XNX)                                                          \
+  wait_vm_n<VW>(XC);                                                                    \
+  name_sc();                                                                            \
+  ring_barrier();                                                                       \
+  load_x(XNX, (I) + 2);                                                                 \
+  stage_w((I) + NSR - 1);                                                               \
+  mma(XC, I);
+  stage_w(0);
+  load_x(x0, 0);
+  stage_w(1);
+  load_x(x1, 1);
+  stage_w(2);
+  for (int i = 0; i < nkb; i += 4) {
+    RING_STEP8(i, x0, x2)
+    RING_STEP8(i + 1, x1, x3)
+    RING_STEP8(i + 2, x2, x0)
+    RING_STEP8(i + 3, x3, x1)
+  }
+#undef RING_STEP8
+  wait_vm_n<0>(x0);
+  keep_live(x1);
+  keep_live(x2);
+  keep_live(x3);
+#pragma unroll
+  for (int i = 0; i < NT; ++i) acc[i] *= sc[i];
+
+  // sum the KW k-groups through LDS (ring is free after the last barrier + wait)
+  __syncthreads();
+  f32x4* red = reinterpret_cast<f32x4*>(sw);        // [wave][nt][lane] = one slot
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) red[(wave * NT + nt) * 64 + lane] = acc[nt];
+  __syncthreads();
+  const float* rf = reinterpret_cast<const float*>(sw);
+  auto sum_k = [&](int m, int nt, int ln, int r) {
+    float v = 0.f;
+#pragma unroll
+    for (int g = 0; g < KW; ++g) v += rf[(((g * MT + m) * NT + nt) * 64 + ln) * 4 + r];
+    return v;
+  };
+  // C/D map of 16x16x32: col = lane & 15 (weight row), row = 4 * (lane >> 4) + r (X row)
+  if constexpr (EPI == EPI_ARGMAX) {
+    // the [rows, NT 16] logit tile through LDS (past the k-group reduction area), 4 lanes per
+    // row -> one (value, id) partial per (row, tile)
+    constexpr int TP = NT * 16 + 1;
+    float* tl = reinterpret_cast<float*>(sw) + 4 * NT * 64 * 4;
+    for (int idx = tid; idx < MT * NT * 256; idx += 256) {
+      const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
+      const int nt = q % NT, m = q / NT;
+      tl[(m * 16 + (ln >> 4) * 4 + r) * TP + nt * 16 + (ln & 15)] = sum_k(m, nt, ln, r);
+    }
+    __syncthreads();
+    const int ntiles = N / (NT * 16);
+    for (int rr = tid >> 2; rr < MT * 16; rr += 64) {
+      float bv = -FLT_MAX;
+      int bi = 0x7fffffff;
+      const int c0 = (tid & 3) * (NT * 4);
+#pragma unroll 4
+      for (int c = c0; c < c0 + NT * 4; ++c) {
+        const int col = n0 + c;
+        if (col < n_valid) argmax_better(bv, bi, bf2f(f2bf(tl[rr * TP + c])), col);
+      }
+#pragma unroll
+      for (int o = 1; o <= 2; o <<= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        argmax_better(bv, bi, ov, oi);
+      }
+      if ((tid & 3) == 0 && rr < M) {
+        pv[(size_t)rr * ntiles + tile] = bv;
+        pi[(size_t)rr * ntiles + tile] = bi;
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < MT * NT; ++e) {
+    const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
+    const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
+    const int nt = q % NT, m = q / NT;
+    const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
+    if (row >= M) continue;
+    if constexpr (EPI == EPI_GLU) {
+      // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns later, both
+      // rounded to bf16 first, as the unfused bf16 GEMM output
+      if ((ln & 8) == 0) {
+        const float gb = bf2f(f2bf(sum_k(m, nt, ln, r))), ub = bf2f(f2bf(sum_k(m, nt, ln + 8, r)));
+        Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_f(gb) * ub);
+      }
+    } else {
+      P[((size_t)slice * M + row) * N + col] = sum_k(m, nt, ln, r);
+    }
+  }
+}
+
+constexpr int MR8 = 32;   // rows of the FP8 ring kernel (MT <= 2)
+
+bool shape8_ok(int M, int N, int K, int S, int bn) {
+  return M >= 1 && M <= MR8 && N >= bn && N % bn == 0 && S >= 1 && K % S == 0 && (K / S) >= NS * BK8 &&
+         (K / S) % (NS * BK8) == 0;
+}
+
+template <int EPI, int NT>
+void launch8(dim3 grid, hipStream_t s, const void* x, const void* w, const float* sc, uint16_t* y, float* p, int M,
+             int N, int K, int Ks, float* pv = nullptr, int* pi = nullptr, int nv = 0) {
+  const int S = grid.y;
+  const int xr = (xcd_knob() && S > 1 && 8 % S == 0 && (grid.x * S) % 8 == 0) ? 1 : 0;
+  const uint16_t* xp = (const uint16_t*)x;
+  const uint8_t* wp = (const uint8_t*)w;
+  if (M <= 16) dgemm8_kernel<EPI, 1, NT><<<grid, 256, 0, s>>>(xp, wp, sc, y, p, M, N, K, Ks, xr, pv, pi, nv);
+  else dgemm8_kernel<EPI, 2, NT><<<grid, 256, 0, s>>>(xp, wp, sc, y, p, M, N, K, Ks, xr, pv, pi, nv);
+}
+}  // namespace
+
+// 2..32-row decode projections over FP8 weights (see dgemm8_kernel; one row works too, the
+// plans send it to the GEMV): Wq [N, K] e4m3fn codes, scale [N] fp32 powers of two.  All
+// return -1, launching nothing, for a shape without an instantiation: more than 32 rows,
+// N % tile, a K slice that is not whole 1024-deep ring turns, pointers off 16 B.
+// fp32 slabs P [S, M, N]; tile_rows: 64
+int docqa_dgemm8_partial(const void* X, const void* Wq, const float* scale, float* P, int M, int N, int K, int S,
+                         int tile_rows, hipStream_t s) {
+  if (M == 0) return 0;
+  if (!X || !Wq || !scale || !P || tile_rows != 64 || !shape8_ok(M, N, K, S, 64) || !docqa_aligned16(X) ||
+      !docqa_aligned16(Wq))
+    return -1;
+  launch8<EPI_PARTIAL, 4>(dim3(N / 64, S), s, X, Wq, scale, nullptr, P, M, N, K, K / S);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// Y [M, N / 2] = silu(gate) * up for the 8-interleaved gate|up codes Wq [N, K] (N = 2 I); 112-row
+// tiles where they give >= 192 workgroups (as docqa_dgemm_glu), else 64-row tiles
+int docqa_dgemm8_glu(const void* X, const void* Wq, const float* scale, void* Y, int M, int N, int K, hipStream_t s) {
+  if (M == 0) return 0;
+  if (!X || !Wq || !scale || !Y || !docqa_aligned16(X) || !docqa_aligned16(Wq)) return -1;
+  if (shape8_ok(M, N, K, 1, 112) && N / 112 >= 192)
+    launch8<EPI_GLU, 7>(dim3(N / 112), s, X, Wq, scale, (uint16_t*)Y, nullptr, M, N, K, K);
+  else if (shape8_ok(M, N, K, 1, 64))
+    launch8<EPI_GLU, 4>(dim3(N / 64), s, X, Wq, scale, (uint16_t*)Y, nullptr, M, N, K, K);
+  else
+    return -1;
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// LM head + greedy pick: out[M] = argmax over the first n_valid columns of bf16(X . W'^T), outv[M]
+// the picked value; ws_v / ws_i: [M, N / 64] per-tile partials
+int docqa_dgemm8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
+                        int* ws_i, int M, int N, int K, int n_valid, hipStream_t s) {
+  if (M == 0) return 0;
+  if (!X || !Wq || !scale || !out || !ws_v || !ws_i || !shape8_ok(M, N, K, 1, 64) || n_valid <= 0 || n_valid > N ||
+      !docqa_aligned16(X) || !docqa_aligned16(Wq))
+    return -1;
+  launch8<EPI_ARGMAX, 4>(dim3(N / 64), s, X, Wq, scale, nullptr, nullptr, M, N, K, K, ws_v, ws_i, n_valid);
+  argmax_merge_kernel<<<M, 256, 0, s>>>(ws_v, ws_i, N / 64, out, outv);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}

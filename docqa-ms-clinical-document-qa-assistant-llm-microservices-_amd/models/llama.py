@@ -286,11 +286,12 @@ class LlamaModel:
     FP8_WEIGHTS = ("qkv", "o", "gate_up", "down")
 
     def quantize_fp8(self) -> None:
-        """FP8 weight streaming for one-row decode steps (TP = 1): every projection and the LM
-        head get a per-row e4m3fn copy (q, s) with power-of-two scales
+        """FP8 weight streaming for decode steps of 1..ops.DGEMM8_MAX_ROWS rows (TP = 1; one row:
+        the GEMV, 2..32 rows: the ring kernel, each where its plan lists the shape): every
+        projection and the LM head get a per-row e4m3fn copy (q, s) with power-of-two scales
         (ops.quantize_fp8_rows), and the resident weights are REPLACED by its exact image
         W' = q * s.  Every kernel that reads W' (prefill, batched decode, mixed steps, sampled
-        logits, the CPU reference) then computes the same model the FP8 GEMV streams from half
+        logits, the CPU reference) then computes the same model the FP8 kernels stream from half
         the bytes, so a request sees one model whatever batch it lands in.  Embedding and
         norms stay as they are.  The copies cost memory (about +50 % of the projections)
         and save none.  Call after random init or load_state_dict_hf, before any decode graph
@@ -350,10 +351,12 @@ class LlamaModel:
         lin = ops.decode_linear if decode else ops.prefill_linear
         M = x.shape[0]
         plans = {}
-        # one-row decode steps of a quantize_fp8() model stream the FP8 copies where
-        # ops.gemv8_plan / gemv8_glu_ok have a kernel (w8: those projections); the rest, and
-        # every other step shape, run on the bf16 image W'
-        use8 = not meta.prefill and self.fp8 is not None and x.is_cuda and M == 1
+        # decode steps of 1..ops.DGEMM8_MAX_ROWS rows of a quantize_fp8() model stream the FP8
+        # copies where the plans list a kernel (w8: those projections) -- one row: the GEMV
+        # (ops.gemv8_plan / gemv8_glu_ok), 2..32 rows: the ring kernel (ops.dgemm8_plan /
+        # dgemm8_glu_ok); the rest, and every other step shape, run on the bf16 image W'
+        use8 = (not meta.prefill and self.fp8 is not None and x.is_cuda
+                and 1 <= M <= ops.DGEMM8_MAX_ROWS)
         w8: dict = {}
         # a short prefill (<= ops.MID_M_MAX prompt tokens: batch-1 serving) has the decode
         # step's shape -- too few rows for the 256 x 256 prefill GEMM's tiles -- so it takes
@@ -381,6 +384,12 @@ class LlamaModel:
                     w8[k] = (S8, R8)
                     plans[k] = (S8, lambda a, w, S=S8, R=R8: ops.gemv8_partial(a, w[0], w[1], S, R))
                     continue
+                S8, t8 = ops.dgemm8_plan(M, *L0[k].shape) if use8 else (0, 64)
+                if S8:
+                    # 2..32 rows, FP8 weights: the ring kernel over the (q, s) copy
+                    w8[k] = (S8, t8)
+                    plans[k] = (S8, lambda a, w, S=S8, t=t8: ops.dgemm8_partial(a, w[0], w[1], S, t))
+                    continue
                 Sg, R = ops.gemv_plan(M, *L0[k].shape) if x.is_cuda else (0, 0)
                 if Sg:
                     # one row: the register-streaming GEMV (no LDS ring) -- QKV / O
@@ -407,6 +416,9 @@ class LlamaModel:
             if use8 and ops.gemv8_glu_ok(M, *L0["gate_up"].shape):
                 w8["gate_up"] = (1, 0)
                 glu = lambda a, w: ops.gemv8_glu(a, w[0], w[1])  # noqa: E731
+            elif use8 and ops.dgemm8_glu_ok(M, *L0["gate_up"].shape):
+                w8["gate_up"] = (1, 0)
+                glu = lambda a, w: ops.dgemm8_glu(a, w[0], w[1])  # noqa: E731
             elif decode and x.is_cuda and ops.gemv_glu_ok(M, *L0["gate_up"].shape):
                 glu = ops.gemv_glu        # one row: the register-streaming GEMV with SwiGLU
             elif small and (ops.pgemm_ok(M, *L0["gate_up"].shape)

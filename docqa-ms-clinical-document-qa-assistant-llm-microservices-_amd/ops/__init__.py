@@ -545,12 +545,17 @@ def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False,
     fused (mgemm.hip EPI_ARGMAX): the [M, vocab] logits never reach HBM.  ``with_values``:
     (ids, picked logit fp32) -- a vocab-parallel shard's candidates for comm.tp_argmax.
     ``fp8``: the (q, s) FP8 copy of ``w`` (:func:`quantize_fp8_rows`, ``w`` its exact image) --
-    a one-row step then streams the codes (dgemm.hip gemv8_kernel EPI_ARGMAX)."""
+    a one-row step then streams the codes (dgemm.hip gemv8_kernel EPI_ARGMAX), a 2..32-row
+    step too where :func:`dgemm8_argmax_ok` (dgemm8_kernel EPI_ARGMAX)."""
     if _gpu(x):
         N, K = w.shape
         if fp8 is not None and n_valid > 0 and gemv8_argmax_ok(x.numel() // K, N, K):
             R, lb = _GEMV8_EPI[K]
             ids, vals = _native().gemv8_argmax_val(x.contiguous(), fp8[0], fp8[1], int(n_valid), R, lb)
+            return (ids, vals) if with_values else ids
+        if fp8 is not None and n_valid > 0 and dgemm8_argmax_ok(x.numel() // K, N, K):
+            # 2..32 rows: the ring kernel over the codes (dgemm.hip dgemm8_kernel EPI_ARGMAX)
+            ids, vals = _native().dgemm8_argmax_val(x.contiguous(), fp8[0], fp8[1], int(n_valid))
             return (ids, vals) if with_values else ids
         if (_GEMV_LM and x.numel() == K and N % 16 == 0 and K % 2048 == 0 and K // 2048 <= 2
                 and n_valid > 0):
@@ -793,6 +798,83 @@ def gemv8_glu_xn(Pin, res_in, res_out, gamma, eps: float, q, s, rows: int = 0, l
         return _native().gemv8_xn(Pin, res_in, res_out, gamma, float(eps), q, s, 1, int(rows) or R, int(lb) or l,
                                   True)
     return gemv_glu_xn(Pin, res_in, res_out, gamma, eps, dequantize_fp8_rows(q, s, res_in.dtype))
+
+
+# 2..DGEMM8_MAX_ROWS-row decode steps over the same (q, s) copies (dgemm.hip dgemm8_kernel: the
+# skinny kernel's LDS-DMA ring filled with codes, 256 per weight row per stage -- K slices of
+# whole 1024-deep ring turns).  33+ rows stay on W': there every wave of the ring kernel would
+# widen every B fragment, four times redundantly, and no 4-m-tile variant is built.
+DGEMM8_MAX_ROWS = 32
+DGEMM8_K = 1024
+_DGEMM8 = os.environ.get("DOCQA_DGEMM8", "1") != "0"
+# (N, K) -> decode buckets (powers of two, engine/llm_engine.py:_bucket) whose step takes the FP8
+# kernel: slab projections, the fused-SwiGLU gate|up, the LM head + argmax.  A (shape, bucket)
+# pair is listed only where benchmarks/bench_dgemm_fp8.py measured the FP8 median below the
+# shipped bf16 plan's with disjoint min..max window ranges (profiles/fp8_dgemm_probe.log);
+# everything else keeps streaming W'.
+# Llama-3-8B / Mistral-7B at M = 2 / 8 / 32, FP8 vs bf16 us: QKV 8.2 / 8.4 / 10.6 vs 11.9 / 12.2 /
+# 13.4, O 6.8 / 7.1 / 8.3 vs 8.3 / 8.6 / 9.3, gate|up 25.7 / 25.1 / 30.7 vs 49.4 / 49.0 / 50.8, down
+# (S = 7) 13.3 / 13.3 / 18.9 vs 21.0 / 20.5 / 22.0, LM head 94.3 / 96.2 / 122.1 vs 193.9 / 191.4 / 194.9
+# (Mistral 31.3 / 32.3 / 39.2 vs 57.1 / 58.1 / 60.9) -- every bucket of every shape won.  The
+# llama3-1b-test preset's rows are the suite's model: its 2048-wide QKV and O (3-6 MB of codes,
+# at most 96 workgroups) are within 10 % of bf16 either way and change sides between runs --
+# both stay on W'.  The (2048, 8192), (16384, 2048) and (32000, 2048) entries below are that
+# preset's down, gate|up and LM head: they are listed for the suite's model, no served model has them.
+_B8 = (2, 4, 8, 16, 32)
+_DGEMM8_SLAB: dict = {(6144, 4096): _B8, (4096, 4096): _B8, (4096, 14336): _B8, (2048, 8192): _B8}
+_DGEMM8_GLU: dict = {(28672, 4096): _B8, (16384, 2048): _B8}
+_DGEMM8_LM: dict = {(128256, 4096): _B8, (32768, 4096): _B8, (32000, 2048): _B8}
+
+
+def _dgemm8_listed(table: dict, M: int, N: int, K: int) -> bool:
+    if not _DGEMM8 or not (2 <= M <= DGEMM8_MAX_ROWS) or N % 64 or K % DGEMM8_K:
+        return False
+    return (1 << (M - 1).bit_length()) in table.get((N, K), ())
+
+
+def dgemm8_splits(N: int, K: int, tile: int = 64, min_wgs: int = 192) -> int:
+    """:func:`decode_plan`'s split rule on the FP8 ring's K granule: the smallest S (slices of
+    whole 1024-deep ring turns) giving >= ``min_wgs`` workgroups, else the most slices there
+    are; 0 where K is not whole ring turns."""
+    if N % tile or K % DGEMM8_K or K < DGEMM8_K:
+        return 0
+    turns = K // DGEMM8_K
+    cands = [S for S in range(1, turns + 1) if turns % S == 0]
+    return next((S for S in cands if (N // tile) * S >= min_wgs), cands[-1])
+
+
+def dgemm8_plan(M: int, N: int, K: int) -> tuple[int, int]:
+    """(split-K count, weight rows per workgroup) of the FP8-weight ring kernel for a 2..32-row
+    decode projection; (0, 64) where the shape has no instantiation or the probe did not show it
+    faster than the bf16 plan (the caller then streams W').  DOCQA_DGEMM8=0 disables."""
+    if not _dgemm8_listed(_DGEMM8_SLAB, M, N, K):
+        return 0, 64
+    return dgemm8_splits(N, K), 64
+
+
+def dgemm8_glu_ok(M: int, N: int, K: int) -> bool:
+    """The 2..32-row gate|up projection with SwiGLU on the FP8-weight ring kernel."""
+    return _dgemm8_listed(_DGEMM8_GLU, M, N, K)
+
+
+def dgemm8_argmax_ok(M: int, N: int, K: int) -> bool:
+    """The 2..32-row LM head + greedy pick on the FP8-weight ring kernel."""
+    return _dgemm8_listed(_DGEMM8_LM, M, N, K)
+
+
+def dgemm8_partial(x, q, s, splits: int, tile_rows: int = 64):
+    """fp32 slabs [S, M, N] of x @ (q * s)^T for 2..32 rows on the FP8-weight ring kernel
+    (:func:`dgemm8_plan`)."""
+    if _gpu(x):
+        return _native().dgemm8_partial(x.contiguous(), q, s, int(splits), int(tile_rows))
+    return dgemm_partial(x, dequantize_fp8_rows(q, s, x.dtype), splits, tile_rows)
+
+
+def dgemm8_glu(x, q, s):
+    """silu(x Wg^T) * (x Wu^T) for 2..32 rows over FP8 8-interleaved gate|up weights."""
+    if _gpu(x):
+        return _native().dgemm8_glu(x.contiguous(), q, s)
+    return glu_linear(x, dequantize_fp8_rows(q, s, x.dtype))
 
 
 NORM_FUSE_ROWS = 4
