@@ -90,6 +90,12 @@ class Settings:
     top_k: int = field(default_factory=lambda: env_int("TOP_K", 3))
     max_new_tokens: int = field(default_factory=lambda: env_int("MAX_NEW_TOKENS", 256))
     temperature: float = field(default_factory=lambda: float(os.getenv("TEMPERATURE", "0")))
+    # llama.cpp-style penalties over the last REPEAT_LAST_N tokens of prompt + output (neutral
+    # by default; Ollama's own defaults are REPEAT_PENALTY=1.1 REPEAT_LAST_N=64, docs/CONFIG.md)
+    repeat_penalty: float = field(default_factory=lambda: float(os.getenv("REPEAT_PENALTY", "1.0")))
+    repeat_last_n: int = field(default_factory=lambda: env_int("REPEAT_LAST_N", 64))
+    presence_penalty: float = field(default_factory=lambda: float(os.getenv("PRESENCE_PENALTY", "0")))
+    frequency_penalty: float = field(default_factory=lambda: float(os.getenv("FREQUENCY_PENALTY", "0")))
     # stop a generation at EOS (the reference's behaviour); STOP_ON_EOS=0 decodes every
     # answer to MAX_NEW_TOKENS (serving benchmarks: random weights emit EOS at random)
     stop_on_eos: bool = field(default_factory=lambda: env_bool("STOP_ON_EOS", "true"))

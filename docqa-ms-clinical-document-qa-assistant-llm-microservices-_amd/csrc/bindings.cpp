@@ -357,6 +357,113 @@ at::Tensor sample(const at::Tensor& logits, const at::Tensor& inv_temp, const at
   return out;
 }
 
+// ---- repeat / presence / frequency penalties over the per-slot token ring ----------------
+// hist [R, W] int32 (W = docqa_penalty_window()), hist_n [R] int32, last_n [R] int32,
+// rep / pres / freq [R] fp32, valid [R] int32 or None (every row)
+static void check_ring(const char* op, int64_t R, const at::Tensor& hist, const at::Tensor& hist_n,
+                       const at::Tensor& last_n, const at::Tensor& rep, const at::Tensor& pres,
+                       const at::Tensor& freq, const c10::optional<at::Tensor>& valid) {
+  TORCH_CHECK(hist.is_cuda() && hist_n.is_cuda() && last_n.is_cuda() && rep.is_cuda() && pres.is_cuda() &&
+                  freq.is_cuda(), op, ": ring state must be GPU tensors");
+  TORCH_CHECK(hist.scalar_type() == at::kInt && hist_n.scalar_type() == at::kInt &&
+                  last_n.scalar_type() == at::kInt, op, ": int32 hist / hist_n / last_n");
+  TORCH_CHECK(rep.scalar_type() == at::kFloat && pres.scalar_type() == at::kFloat &&
+                  freq.scalar_type() == at::kFloat, op, ": fp32 penalties");
+  TORCH_CHECK(hist.dim() == 2 && hist.size(0) == R && hist.size(1) == docqa_penalty_window() &&
+                  hist.is_contiguous(), op, ": hist must be contiguous [rows, PENALTY_WINDOW]");
+  TORCH_CHECK(hist_n.numel() == R && last_n.numel() == R && rep.numel() == R && pres.numel() == R &&
+                  freq.numel() == R, op, ": per-row parameters must have one entry per row");
+  TORCH_CHECK(hist_n.is_contiguous() && last_n.is_contiguous() && rep.is_contiguous() &&
+                  pres.is_contiguous() && freq.is_contiguous(), op, ": contiguous per-row parameters");
+  if (valid.has_value() && valid->defined())
+    TORCH_CHECK(valid->is_cuda() && valid->scalar_type() == at::kInt && valid->numel() == R &&
+                    valid->is_contiguous(), op, ": valid must be contiguous int32 [rows]");
+}
+
+static const int* valid_ptr(const c10::optional<at::Tensor>& valid) {
+  return valid.has_value() && valid->defined() ? valid->data_ptr<int>() : nullptr;
+}
+
+int64_t penalty_window() { return docqa_penalty_window(); }
+
+// in place on fp32 logits [R, V] (row stride >= V): only the window's entries are touched
+void apply_penalties(at::Tensor logits, const at::Tensor& hist, const at::Tensor& hist_n,
+                     const at::Tensor& last_n, const at::Tensor& rep, const at::Tensor& pres,
+                     const at::Tensor& freq, const c10::optional<at::Tensor>& valid) {
+  CHECK_GPU(logits);
+  TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.dim() == 2 && logits.stride(1) == 1,
+              "apply_penalties wants fp32 [rows, V] with unit stride");
+  const int64_t R = logits.size(0), V = logits.size(1), ld = logits.stride(0);
+  TORCH_CHECK(R == 0 || (ld >= V && R * ld < (int64_t(1) << 40)), "apply_penalties: row stride below V");
+  check_ring("apply_penalties", R, hist, hist_n, last_n, rep, pres, freq, valid);
+  c10::DeviceGuard g(logits.device());
+  CHECK_RC(docqa_apply_penalties(logits.data_ptr<float>(), (int)R, (int)V, (int)ld, hist.data_ptr<int>(),
+                                 (int)hist.size(1), hist_n.data_ptr<int>(), last_n.data_ptr<int>(),
+                                 rep.data_ptr<float>(), pres.data_ptr<float>(), freq.data_ptr<float>(),
+                                 valid_ptr(valid), stream()), "apply_penalties");
+}
+
+// argmax over t < n_valid of the penalised bf16 / fp32 logits [R, V] -> int64 [R], ties to the
+// lowest index.  CLOBBERS logits: the window tokens' entries are overwritten.
+at::Tensor penalized_argmax(at::Tensor logits, int64_t n_valid, const at::Tensor& hist,
+                            const at::Tensor& hist_n, const at::Tensor& last_n, const at::Tensor& rep,
+                            const at::Tensor& pres, const at::Tensor& freq,
+                            const c10::optional<at::Tensor>& valid) {
+  CHECK_GPU(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "penalized_argmax wants [rows, V] with unit stride");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "penalized_argmax: bf16 or fp32 logits");
+  const int64_t R = logits.size(0), V = logits.size(1), ld = logits.stride(0);
+  TORCH_CHECK(n_valid >= 1 && n_valid <= V, "penalized_argmax: n_valid must be in [1, V]");
+  TORCH_CHECK(R == 0 || ld >= V, "penalized_argmax: row stride below V");
+  TORCH_CHECK(ld % (bf ? 8 : 4) == 0, "penalized_argmax: row stride must be a multiple of 16 bytes");
+  CHECK_ALIGN16(logits);
+  check_ring("penalized_argmax", R, hist, hist_n, last_n, rep, pres, freq, valid);
+  int splits = (int)((n_valid + 8191) / 8192);
+  if (splits > 64) splits = 64;
+  if (splits < 1) splits = 1;
+  const int W = docqa_penalty_window();
+  c10::DeviceGuard g(logits.device());
+  auto ws_v = at::empty({R * splits}, logits.options().dtype(at::kFloat));
+  auto ws_i = at::empty({R * splits}, logits.options().dtype(at::kInt));
+  auto pen_v = at::empty({R * W}, logits.options().dtype(at::kFloat));
+  auto pen_i = at::empty({R * W}, logits.options().dtype(at::kInt));
+  auto out = at::empty({R}, logits.options().dtype(at::kLong));
+  CHECK_RC(docqa_penalized_argmax(logits.data_ptr(), (int)R, (int)V, (int)ld, (int)n_valid, bf ? 1 : 0,
+                                  hist.data_ptr<int>(), (int)hist.size(1), hist_n.data_ptr<int>(),
+                                  last_n.data_ptr<int>(), rep.data_ptr<float>(), pres.data_ptr<float>(),
+                                  freq.data_ptr<float>(), valid_ptr(valid), ws_v.data_ptr<float>(),
+                                  ws_i.data_ptr<int>(), splits, pen_v.data_ptr<float>(), pen_i.data_ptr<int>(),
+                                  out.data_ptr<int64_t>(), stream()), "penalized_argmax");
+  return out;
+}
+
+// decode_advance + the ring: hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1 for valid rows
+void decode_advance_hist(const at::Tensor& nxt, at::Tensor out, at::Tensor tokens, at::Tensor positions,
+                         at::Tensor context_lens, const at::Tensor& valid, at::Tensor hist,
+                         at::Tensor hist_n) {
+  CHECK_GPU(nxt);
+  const int B = nxt.numel();
+  TORCH_CHECK(nxt.scalar_type() == at::kLong && out.scalar_type() == at::kLong &&
+                  tokens.scalar_type() == at::kInt && positions.scalar_type() == at::kInt &&
+                  context_lens.scalar_type() == at::kInt && valid.scalar_type() == at::kInt &&
+                  hist.scalar_type() == at::kInt && hist_n.scalar_type() == at::kInt,
+              "decode_advance_hist: int64 nxt/out, int32 state");
+  TORCH_CHECK(out.numel() == B && tokens.numel() == B && positions.numel() == B &&
+                  context_lens.numel() == B && valid.numel() == B && hist_n.numel() == B,
+              "decode_advance_hist: B mismatch");
+  TORCH_CHECK(hist.is_cuda() && hist_n.is_cuda() && hist.dim() == 2 && hist.size(0) == B &&
+                  hist.size(1) == docqa_penalty_window(), "decode_advance_hist: hist [B, PENALTY_WINDOW]");
+  TORCH_CHECK(nxt.is_contiguous() && out.is_contiguous() && tokens.is_contiguous() &&
+                  positions.is_contiguous() && context_lens.is_contiguous() && valid.is_contiguous() &&
+                  hist.is_contiguous() && hist_n.is_contiguous(), "decode_advance_hist: contiguous tensors");
+  c10::DeviceGuard g(nxt.device());
+  CHECK_RC(docqa_decode_advance_hist(nxt.data_ptr<int64_t>(), out.data_ptr<int64_t>(), tokens.data_ptr<int>(),
+                                     positions.data_ptr<int>(), context_lens.data_ptr<int>(),
+                                     valid.data_ptr<int>(), hist.data_ptr<int>(), (int)hist.size(1),
+                                     hist_n.data_ptr<int>(), B, stream()), "decode_advance_hist");
+}
+
 // optional LPT dispatch order of the decode workgroups (int32 permutation of [0, B))
 static const int* order_ptr(const c10::optional<at::Tensor>& order, int B) {
   if (!order.has_value() || !order->defined()) return nullptr;
@@ -1434,6 +1541,13 @@ TORCH_LIBRARY(docqa, m) {
   m.def("decode_slots(Tensor block_tables, Tensor positions, Tensor valid, int BS) -> Tensor");
   m.def("decode_advance(Tensor nxt, Tensor(a!) out, Tensor(b!) tokens, Tensor(c!) positions, Tensor(d!) context_lens, Tensor valid) -> ()");
   m.def("sample(Tensor logits, Tensor inv_temp, Tensor top_k, Tensor top_p, Tensor u) -> Tensor");
+  m.def("penalty_window() -> int", &penalty_window);
+  m.def("apply_penalties(Tensor(a!) logits, Tensor hist, Tensor hist_n, Tensor last_n, Tensor rep_pen, "
+        "Tensor pres_pen, Tensor freq_pen, Tensor? valid=None) -> ()");
+  m.def("penalized_argmax(Tensor(a!) logits, int n_valid, Tensor hist, Tensor hist_n, Tensor last_n, "
+        "Tensor rep_pen, Tensor pres_pen, Tensor freq_pen, Tensor? valid=None) -> Tensor");
+  m.def("decode_advance_hist(Tensor nxt, Tensor(a!) out, Tensor(b!) tokens, Tensor(c!) positions, "
+        "Tensor(d!) context_lens, Tensor valid, Tensor(e!) hist, Tensor(f!) hist_n) -> ()");
   m.def("paged_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor context_lens, int Hq, int max_context, float scale, Tensor? order=None) -> Tensor");
   m.def("flash_prefill(Tensor qkv, Tensor cu_seqlens, int max_len, int Hq, int Hkv, int D, "
@@ -1533,6 +1647,9 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("decode_slots", &decode_slots);
   m.impl("decode_advance", &decode_advance);
   m.impl("sample", &sample);
+  m.impl("apply_penalties", &apply_penalties);
+  m.impl("penalized_argmax", &penalized_argmax);
+  m.impl("decode_advance_hist", &decode_advance_hist);
   m.impl("paged_decode", &paged_decode);
   m.impl("flash_prefill", &flash_prefill);
   m.impl("knn", &knn);

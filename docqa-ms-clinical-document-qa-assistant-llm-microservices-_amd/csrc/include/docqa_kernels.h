@@ -41,6 +41,22 @@ int docqa_sample(const float* logits, int rows, int V, int ld, const float* inv_
                  const int* top_k, const float* top_p, const float* u, int64_t* out,
                  hipStream_t s);
 
+// repeat / presence / frequency penalties over a per-row token ring hist [rows, W] (W must be
+// docqa_penalty_window()), hist_n [rows] tokens appended so far; valid may be null (all rows)
+int docqa_penalty_window();
+int docqa_apply_penalties(float* logits, int rows, int V, int ld, const int* hist, int W,
+                          const int* hist_n, const int* last_n, const float* rep, const float* pres,
+                          const float* freq, const int* valid, hipStream_t s);
+// argmax over t < n_valid of the penalised logits; CLOBBERS the window tokens' logits
+int docqa_penalized_argmax(void* logits, int rows, int V, int ld, int n_valid, int is_bf16,
+                           const int* hist, int W, const int* hist_n, const int* last_n,
+                           const float* rep, const float* pres, const float* freq, const int* valid,
+                           float* ws_v, int* ws_i, int splits, float* pen_v, int* pen_i,
+                           int64_t* out, hipStream_t s);
+int docqa_decode_advance_hist(const int64_t* nxt, int64_t* out, int* tokens, int* positions,
+                              int* context_lens, const int* valid, int* hist, int W, int* hist_n,
+                              int B, hipStream_t s);
+
 int docqa_paged_decode(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                        const int* block_tables, int maxb, const int* context_lens, void* out,
                        int out_stride, float* tmp_out, float* tmp_ml, int B, int Hq, int Hkv,

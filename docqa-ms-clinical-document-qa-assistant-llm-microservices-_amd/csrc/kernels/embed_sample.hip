@@ -9,6 +9,9 @@
 //  * sample_rows      : temperature / top-k / top-p sampling from fp32 logits with a
 //                       per-row uniform draw supplied by the caller (graph-capturable:
 //                       no RNG state inside the kernel)
+//  * penalties         : llama.cpp's repeat / presence / frequency penalties over a per-slot
+//                       token ring: apply_penalties (in front of sample_rows), the penalised
+//                       greedy pick (extract + argmax pass 1 + merge) and decode_advance_hist
 #include "docqa_common.h"
 #include <float.h>
 
@@ -413,6 +416,238 @@ int docqa_decode_advance(const int64_t* nxt, int64_t* out, int* tokens, int* pos
                          int* context_lens, const int* valid, int B, hipStream_t s) {
   if (B == 0) return 0;
   decode_advance_kernel<<<(B + 255) / 256, 256, 0, s>>>(nxt, out, tokens, positions, context_lens, valid, B);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// Repeat / presence / frequency penalties (llama.cpp's penalty sampler, which Ollama runs).
+// Token history is a ring per decode slot: hist [B, kPenaltyWindow] int32, hist_n [B] the
+// number of tokens appended so far (only grows); stream entry j sits at hist[b, j % W].
+// For each DISTINCT token t of the newest n = min(hist_n, last_n, W) entries with count c:
+//   l = (l <= 0) ? l * rp : l / rp;   l = l - (c * fp + pp)
+// every operation individually rounded in fp32 (no fma contraction, no reciprocal), so the
+// result is bitwise that of the torch fp32 reference (ops/reference.py).
+constexpr int kPenaltyWindow = 256;
+constexpr int kMergeSplitsMax = 64;   // vocab splits of argmax_pass1 the merge kernel takes
+
+// Row parameters are neutral (nothing to apply): the row's logits stay bitwise untouched.
+__device__ __forceinline__ bool penalty_neutral(int last_n, float rp, float pp, float fp) {
+  return last_n == 0 || (rp == 1.f && pp == 0.f && fp == 0.f);
+}
+
+// One 256-thread workgroup per row: the newest n ring entries go to LDS (thread j holds the
+// j-th oldest of them); returns this thread's token, or -1 unless it is the FIRST occurrence
+// of an in-range token (ids outside [0, V) are ignored), with its count in the window in
+// *count.  Plain compares against the LDS copy (<= 256 x 256), no atomics, no sort: exactly
+// one thread acts per distinct token, so the result is deterministic.
+__device__ __forceinline__ int penalty_window_token(const int* __restrict__ hist_row, int hist_n,
+                                                    int last_n, int V, int* s_tok, int* count) {
+  int n = hist_n < kPenaltyWindow ? hist_n : kPenaltyWindow;
+  if (n < 0) n = 0;
+  if (last_n >= 0 && last_n < n) n = last_n;   // -1 (any negative) / above capacity: the capacity
+  const int j = threadIdx.x;
+  int t = -1;
+  if (j < n) {
+    // stream index hist_n - n + j, >= 0; the ring index needs only its low 8 bits
+    t = hist_row[(unsigned)(hist_n - n + j) % (unsigned)kPenaltyWindow];
+    if ((unsigned)t >= (unsigned)V) t = -1;
+  }
+  s_tok[j] = t;
+  __syncthreads();
+  if (t < 0) return -1;
+  int c = 0;
+  bool first = true;
+  for (int k = 0; k < n; ++k) {
+    const bool same = s_tok[k] == t;
+    c += same ? 1 : 0;
+    first = first && !(same && k < j);
+  }
+  *count = c;
+  return first ? t : -1;
+}
+
+// The __f*_rn helpers of the HIP headers are plain operators, and hipcc contracts by default
+// (c * fp + pp into one fma, l * rp - x likewise) -- in the front end, which the pragma below
+// switches off for this function, AND in the back end, whose fusion is a global option that
+// ignores the pragma.  So every intermediate also passes through an empty asm that only
+// pins it in a VGPR: the back end cannot see the multiply behind the add it would fuse.
+__device__ __forceinline__ float rounded(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+__device__ __forceinline__ float penalize(float l, int c, float rp, float pp, float fp) {
+#pragma clang fp contract(off)
+  l = rounded((l <= 0.f) ? __fmul_rn(l, rp) : __fdiv_rn(l, rp));
+  const float cf = rounded(__fmul_rn((float)c, fp));
+  return __fsub_rn(l, rounded(__fadd_rn(cf, pp)));
+}
+
+// In place on fp32 logits [R, ld]: touches only the window's entries, never scans the row.
+__global__ __launch_bounds__(256) void apply_penalties_kernel(
+    float* __restrict__ logits, int V, int ld, const int* __restrict__ hist,
+    const int* __restrict__ hist_n, const int* __restrict__ last_n, const float* __restrict__ rep,
+    const float* __restrict__ pres, const float* __restrict__ freq, const int* __restrict__ valid) {
+  __shared__ int s_tok[kPenaltyWindow];
+  const int row = blockIdx.x;
+  if (valid != nullptr && valid[row] == 0) return;
+  const int ln = last_n[row];
+  const float rp = rep[row], pp = pres[row], fp = freq[row];
+  if (penalty_neutral(ln, rp, pp, fp)) return;
+  int c = 0;
+  const int t = penalty_window_token(hist + (size_t)row * kPenaltyWindow, hist_n[row], ln, V, s_tok, &c);
+  if (t < 0) return;
+  float* p = logits + (size_t)row * ld + t;
+  *p = penalize(*p, c, rp, pp, fp);
+}
+
+// penalised greedy, step 1: the window tokens' penalised values go to (pen_v, pen_i)
+// [R, kPenaltyWindow] (pen_i -1: no entry) and their logits are overwritten with the lowest
+// finite value, so the plain argmax over the row that follows sees only the rest.
+template <bool BF16>
+__global__ __launch_bounds__(256) void penalty_extract_kernel(
+    void* __restrict__ logits, int V, int ld, const int* __restrict__ hist,
+    const int* __restrict__ hist_n, const int* __restrict__ last_n, const float* __restrict__ rep,
+    const float* __restrict__ pres, const float* __restrict__ freq, const int* __restrict__ valid,
+    float* __restrict__ pen_v, int* __restrict__ pen_i) {
+  __shared__ int s_tok[kPenaltyWindow];
+  const int row = blockIdx.x;
+  const size_t o = (size_t)row * kPenaltyWindow + threadIdx.x;
+  const int ln = last_n[row];
+  const float rp = rep[row], pp = pres[row], fp = freq[row];
+  int t = -1, c = 0;
+  if ((valid == nullptr || valid[row] != 0) && !penalty_neutral(ln, rp, pp, fp))   // row-uniform
+    t = penalty_window_token(hist + (size_t)row * kPenaltyWindow, hist_n[row], ln, V, s_tok, &c);
+  pen_i[o] = t;
+  if (t < 0) return;
+  float l;
+  if constexpr (BF16) {
+    uint16_t* p = reinterpret_cast<uint16_t*>(logits) + (size_t)row * ld + t;
+    l = bf2f(*p);
+    *p = 0xFF7F;   // lowest finite bf16
+  } else {
+    float* p = reinterpret_cast<float*>(logits) + (size_t)row * ld + t;
+    l = *p;
+    *p = -FLT_MAX;
+  }
+  pen_v[o] = penalize(l, c, rp, pp, fp);
+}
+
+// penalised greedy, step 3: merge the split winners of argmax_pass1 over the rest of the row
+// with the <= kPenaltyWindow penalised values; ties to the lowest index.  A split winner
+// that is itself a window token (its overwritten value won a slice that holds nothing
+// larger) is dropped: its real value is among the penalised ones.  Restores nothing.
+// Limits, for logits at or below the sentinel (bf16 0xFF7F / -FLT_MAX; real logits are finite
+// and far above it): when a slice's winner is dropped, a non-window entry of that slice that
+// EQUALS the sentinel at a higher index is lost with it, and -inf entries never enter at
+// all (argmax_pass1 starts from -FLT_MAX), so a row with nothing else left falls to a
+// penalised entry, or to id 0 when it has none.
+__global__ __launch_bounds__(256) void penalty_merge_kernel(const float* __restrict__ pv,
+                                                            const int* __restrict__ pi, int splits,
+                                                            const float* __restrict__ pen_v,
+                                                            const int* __restrict__ pen_i,
+                                                            int64_t* __restrict__ out) {
+  __shared__ int s_pi[kMergeSplitsMax];
+  __shared__ int s_drop[kMergeSplitsMax];
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const size_t o = (size_t)row * kPenaltyWindow + tid;
+  const int mine = pen_i[o];
+  if (tid < splits) { s_pi[tid] = pi[row * splits + tid]; s_drop[tid] = 0; }
+  __syncthreads();
+  float bv = -FLT_MAX;
+  int bi = 0x7fffffff;
+  if (mine >= 0) {
+    better(bv, bi, pen_v[o], mine);
+    for (int s = 0; s < splits; ++s)
+      if (s_pi[s] == mine) s_drop[s] = 1;   // every writer stores the same value
+  }
+  __syncthreads();
+  if (tid < splits && !s_drop[tid]) better(bv, bi, pv[row * splits + tid], s_pi[tid]);
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    const float ov = __shfl_xor(bv, w, 64);
+    const int oi = __shfl_xor(bi, w, 64);
+    better(bv, bi, ov, oi);
+  }
+  if ((tid & 63) == 0) { sv[tid >> 6] = bv; si[tid >> 6] = bi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
+    out[row] = bi == 0x7fffffff ? 0 : bi;
+  }
+}
+
+//   decode_advance + the ring: hist[i, hist_n[i] % W] = nxt[i]; hist_n[i] += 1 (valid rows)
+__global__ __launch_bounds__(256) void decode_advance_hist_kernel(
+    const int64_t* __restrict__ nxt, int64_t* __restrict__ out, int* __restrict__ tokens,
+    int* __restrict__ pos, int* __restrict__ ctx, const int* __restrict__ valid,
+    int* __restrict__ hist, int* __restrict__ hist_n, int B) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B) return;
+  const int64_t t = nxt[i];
+  const int v = valid[i];
+  out[i] = t;
+  tokens[i] = (int)t;
+  pos[i] += v;
+  ctx[i] += v;
+  if (v) {
+    const int n = hist_n[i];
+    hist[(size_t)i * kPenaltyWindow + (unsigned)n % (unsigned)kPenaltyWindow] = (int)t;
+    hist_n[i] = n + 1;
+  }
+}
+
+int docqa_penalty_window() { return kPenaltyWindow; }
+
+int docqa_apply_penalties(float* logits, int rows, int V, int ld, const int* hist, int W,
+                          const int* hist_n, const int* last_n, const float* rep, const float* pres,
+                          const float* freq, const int* valid, hipStream_t s) {
+  if (rows == 0) return 0;
+  if (W != kPenaltyWindow || V <= 0 || ld < V) return -1;
+  if (((uintptr_t)logits & 3u) != 0) return -1;
+  apply_penalties_kernel<<<rows, 256, 0, s>>>(logits, V, ld, hist, hist_n, last_n, rep, pres, freq, valid);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// Clobbers `logits` (the window tokens' entries).  ws_v / ws_i: >= rows * splits; pen_v /
+// pen_i: >= rows * W.  The [rows, V] logits are read once (by argmax_pass1).
+int docqa_penalized_argmax(void* logits, int rows, int V, int ld, int n_valid, int is_bf16,
+                           const int* hist, int W, const int* hist_n, const int* last_n,
+                           const float* rep, const float* pres, const float* freq, const int* valid,
+                           float* ws_v, int* ws_i, int splits, float* pen_v, int* pen_i,
+                           int64_t* out, hipStream_t s) {
+  if (rows == 0) return 0;
+  if (W != kPenaltyWindow || n_valid <= 0 || n_valid > V || ld < V || splits < 1 ||
+      splits > kMergeSplitsMax) return -1;
+  if (is_bf16 && ld % 8 != 0) return -1;
+  if (!is_bf16 && ld % 4 != 0) return -1;
+  if (!docqa_aligned16(logits)) return -1;
+  dim3 g1(splits, rows);
+  if (is_bf16) {
+    penalty_extract_kernel<true><<<rows, 256, 0, s>>>(logits, n_valid, ld, hist, hist_n, last_n, rep, pres,
+                                                      freq, valid, pen_v, pen_i);
+    argmax_pass1<true><<<g1, 256, 0, s>>>(logits, n_valid, ld, splits, ws_v, ws_i);
+  } else {
+    penalty_extract_kernel<false><<<rows, 256, 0, s>>>(logits, n_valid, ld, hist, hist_n, last_n, rep, pres,
+                                                       freq, valid, pen_v, pen_i);
+    argmax_pass1<false><<<g1, 256, 0, s>>>(logits, n_valid, ld, splits, ws_v, ws_i);
+  }
+  penalty_merge_kernel<<<rows, 256, 0, s>>>(ws_v, ws_i, splits, pen_v, pen_i, out);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+int docqa_decode_advance_hist(const int64_t* nxt, int64_t* out, int* tokens, int* positions,
+                              int* context_lens, const int* valid, int* hist, int W, int* hist_n,
+                              int B, hipStream_t s) {
+  if (B == 0) return 0;
+  if (W != kPenaltyWindow) return -1;
+  decode_advance_hist_kernel<<<(B + 255) / 256, 256, 0, s>>>(nxt, out, tokens, positions, context_lens,
+                                                             valid, hist, hist_n, B);
   DOCQA_CHECK_LAUNCH();
   return 0;
 }

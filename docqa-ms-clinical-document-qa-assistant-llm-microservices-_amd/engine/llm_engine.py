@@ -48,6 +48,25 @@ class SamplingParams:
     top_p: float = 1.0
     stop_on_eos: bool = True
     seed: int = 0
+    # llama.cpp's penalty sampler over the last ``repeat_last_n`` tokens of prompt + output
+    # (0 disables; -1 or more than ops.PENALTY_WINDOW: that capacity).  Per distinct token
+    # with count c: l = l <= 0 ? l * repeat_penalty : l / repeat_penalty, then
+    # l -= c * frequency_penalty + presence_penalty, before temperature / top-k / top-p.
+    repeat_penalty: float = 1.0
+    repeat_last_n: int = 64
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    @property
+    def neutral(self) -> bool:
+        """No penalty applies: the request decodes through the unpenalised kernels."""
+        return self.repeat_last_n == 0 or (self.repeat_penalty == 1.0 and self.presence_penalty == 0.0
+                                           and self.frequency_penalty == 0.0)
+
+    @property
+    def fused_greedy_ok(self) -> bool:
+        """Greedy AND neutral: the LM head's fused argmax picks the token."""
+        return self.temperature <= 0.0 and self.neutral
 
 
 @dataclass
@@ -123,6 +142,18 @@ def _prefill_inputs(prompts: list[list[int]], tables: list[list[int]], cached: l
         tbm[r, :len(t)] = t
     slots = tbm[rows, pos // BS] * BS + pos % BS
     return ids, pos.astype(np.int32), slots.astype(np.int32), cu
+
+
+def ring_of(stream: list[int], W: int) -> tuple[torch.Tensor, int]:
+    """The penalty ring of a token stream (prompt + output so far): row [W] int32 with stream
+    entry j at index j % W for the newest min(len, W) entries, and the stream length."""
+    n = len(stream)
+    row = torch.zeros(W, dtype=torch.int32)
+    m = min(n, W)
+    if m:
+        idx = torch.arange(n - m, n) % W
+        row[idx] = torch.tensor(stream[n - m:], dtype=torch.int32)
+    return row, n
 
 
 def _upload(dst: torch.Tensor, src: torch.Tensor) -> None:
@@ -227,6 +258,15 @@ class _DecodeGraph:
         self.top_k = torch.zeros(bp, dtype=torch.int32, device=dev)
         self.top_p = torch.ones(bp, dtype=torch.float32, device=dev)
         self.out = torch.zeros(bp, dtype=torch.long, device=dev)
+        # penalties: the token ring of each slot (prompt + output; stream entry j at
+        # hist[b, j % W]) and the per-slot parameters; only the penalised graphs touch them
+        self.hist = torch.zeros(bp, ops.PENALTY_WINDOW, dtype=torch.int32, device=dev)
+        self.hist_n = torch.zeros(bp, dtype=torch.int32, device=dev)
+        self.last_n = torch.zeros(bp, dtype=torch.int32, device=dev)
+        self.rep_pen = torch.ones(bp, dtype=torch.float32, device=dev)
+        self.pres_pen = torch.zeros(bp, dtype=torch.float32, device=dev)
+        self.freq_pen = torch.zeros(bp, dtype=torch.float32, device=dev)
+        self.penalized = False
         # cascade decode: block ids / length of the prompt prefix every row shares
         self.shared_table = torch.zeros(eng.max_blocks_per_seq, dtype=torch.int32, device=dev)
         self.shared_len = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -254,7 +294,7 @@ class _DecodeGraph:
         g = cls.__new__(cls)
         g.bp = bp
         for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
-                     "top_k", "top_p", "out"):
+                     "top_k", "top_p", "out", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen"):
             setattr(g, name, getattr(master, name)[:bp])
         g.shared_table, g.shared_len = master.shared_table, master.shared_len
         g.order = torch.arange(bp, dtype=torch.int32, device=master.tokens.device)
@@ -262,6 +302,7 @@ class _DecodeGraph:
         g.groups = _identity_groups(bp, master.tokens.device, master.hkv)
         g.groups_key = None
         g.cascade, g.greedy, g.graph = False, True, None
+        g.penalized = False
         g.groups_fit = master.groups_fit
         g.hkv = master.hkv
         return g
@@ -433,6 +474,17 @@ class LLMEngine:
     # ------------------------------------------------------------------ decode step
     def _step_body(self, g: _DecodeGraph) -> None:
         meta = self._decode_meta(g)
+        if g.penalized:
+            # penalised flavours: [B, vocab] logits, the pick under the slots' penalties, and
+            # the new token joins each slot's ring inside the step
+            logits = self.model.forward(g.tokens, meta, self.kv.caches)
+            if g.greedy:
+                nxt = self._penalized_greedy(logits, g)
+            else:
+                nxt = self._select(logits, g)
+            ops.decode_advance_hist(nxt.long().contiguous(), g.out, g.tokens, g.positions, g.context_lens,
+                                    g.valid, g.hist, g.hist_n)
+            return
         if g.greedy:
             # greedy: the LM head's argmax is fused into its GEMM (no [B, vocab] logits)
             nxt = self.model.forward(g.tokens, meta, self.kv.caches, greedy_ids=True)
@@ -464,16 +516,33 @@ class LLMEngine:
         if g.greedy:
             return self.model.greedy(logits)
         full = self.model.full_logits(logits).float()
+        if g.penalized:
+            if not full.is_contiguous() or full.data_ptr() == logits.data_ptr():
+                full = full.clone(memory_format=torch.contiguous_format)   # never the caller's logits
+            R = full.shape[0]   # the first-token pick covers the batch's rows, a step the bucket's
+            ops.apply_penalties(full, g.hist[:R], g.hist_n[:R], g.last_n[:R], g.rep_pen[:R], g.pres_pen[:R],
+                                g.freq_pen[:R], g.valid[:R])
         u = torch.rand(full.shape[0], device=full.device)
         return ops.sample(full, g.inv_temp, g.top_k, g.top_p, u)
 
-    def _get_graph(self, bp: int, greedy: bool, cascade: bool = False, fit: bool = True) -> _DecodeGraph:
+    def _penalized_greedy(self, logits, g: _DecodeGraph):
+        """Greedy ids under the slots' penalties from the LM head's logits (gathered over the
+        vocab at TP > 1): one pass over the [R, vocab] logits, no fp32 copy, no sampler.
+        ``logits`` is clobbered."""
+        full = self.model.full_logits(logits)
+        R = full.shape[0]
+        return ops.penalized_argmax(full, full.shape[1], g.hist[:R], g.hist_n[:R], g.last_n[:R], g.rep_pen[:R],
+                                    g.pres_pen[:R], g.freq_pen[:R], g.valid[:R])
+
+    def _get_graph(self, bp: int, greedy: bool, cascade: bool = False, fit: bool = True,
+                   penalized: bool = False) -> _DecodeGraph:
         fit = fit or self.max_blocks_per_seq <= ops.GROUP_MAX_BLOCKS
-        key = (bp, greedy, cascade, fit)
+        key = (bp, greedy, cascade, fit, penalized)
         g = self._graphs.get(key)
         if g is None:
             g = _DecodeGraph(self, bp)
             g.greedy = greedy
+            g.penalized = penalized
             g.cascade = cascade
             g.groups_fit = fit
             self._graphs[key] = g
@@ -642,14 +711,16 @@ class LLMEngine:
             rot = int(os.environ.get("DOCQA_TUNE_ROTATE_MB", "512"))
             if rot > 0 and hasattr(tunable, "set_rotating_buffer_size"):
                 tunable.set_rotating_buffer_size(rot)
-        saved = [t.clone() for t in (g.tokens, g.positions, g.context_lens)]
+        # the eager warm-up step advances the slot state (and the penalised flavours' rings)
+        state = (g.tokens, g.positions, g.context_lens) + ((g.hist, g.hist_n) if g.penalized else ())
+        saved = [t.clone() for t in state]
         try:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self._step_body(g)
             torch.cuda.current_stream().wait_stream(s)
-            for t, v in zip((g.tokens, g.positions, g.context_lens), saved):
+            for t, v in zip(state, saved):
                 t.copy_(v)
             if tune and tunable is not None:
                 tunable.tuning_enable(False)
@@ -667,12 +738,12 @@ class LLMEngine:
         finally:
             if tune and tunable is not None:
                 tunable.enable(False)
-        for t, v in zip((g.tokens, g.positions, g.context_lens), saved):
+        for t, v in zip(state, saved):
             t.copy_(v)
         g.graph = graph
 
     @torch.inference_mode()
-    def warm_graphs(self, batch: int, greedy: bool = True) -> None:
+    def warm_graphs(self, batch: int, greedy: bool = True, penalized: bool = False) -> None:
         """Capture the decode graphs (plain and cascade) of the bucket serving ``batch``
         sequences now, with empty slots (valid 0: nothing is written to the KV cache), so
         the first batch that hits the cascade path does not pay a capture / GEMM tuning."""
@@ -680,7 +751,7 @@ class LLMEngine:
             return
         bp = _bucket(batch, self.max_batch)
         for cascade in ([False, True] if self.cascade else [False]):
-            g = self._get_graph(bp, greedy, cascade)
+            g = self._get_graph(bp, greedy, cascade, penalized=penalized)
             if g.graph is None:
                 for t in (g.valid, g.positions, g.context_lens, g.tokens):
                     t.zero_()
@@ -832,13 +903,15 @@ class LLMEngine:
         use_pc = self._use_pc
         try:
             greedy = params.temperature <= 0.0
+            penalized = not params.neutral
             t0 = time.perf_counter()
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if cuda else None
             if cuda:
                 ev[0].record()
             self.queue_prefix_copies(r)
             with tracing.span("engine.prefill", seqs=B, tokens=sum(lens) - sum(cached)):
-                logits = self._prefill(prompts, tables, cached, greedy=greedy)
+                # penalised requests pick their first token under the penalties too: logits
+                logits = self._prefill(prompts, tables, cached, greedy=greedy and not penalized)
             if use_pc:
                 with tracing.span("engine.register", seqs=B):
                     self.register_prefixes(prompts, tables, r.keys)
@@ -848,7 +921,8 @@ class LLMEngine:
             self.stats.attn_batches += 1
             fit = self.groups_fit([n + params.max_new_tokens for n in lens])
             grouped = nshared > 0 or self.group_without_prefix(B, fit)
-            g = self._get_graph(_bucket(B, self.max_batch) if self.use_graphs else B, greedy, grouped, fit)
+            g = self._get_graph(_bucket(B, self.max_batch) if self.use_graphs else B, greedy, grouped, fit,
+                                penalized)
             if grouped:
                 g.shared_len.fill_(0)
             if nshared:
@@ -879,7 +953,25 @@ class LLMEngine:
                 g.top_p.fill_(params.top_p)
                 if params.seed:
                     torch.manual_seed(params.seed)
-            first = logits if greedy else self._select(logits, g)
+            if penalized:
+                # the ring starts as each prompt's tail (stream entry j at hist[b, j % W])
+                W = ops.PENALTY_WINDOW
+                hist = torch.zeros(g.bp, W, dtype=torch.int32)
+                hn = torch.zeros(g.bp, dtype=torch.int32)
+                for i, p in enumerate(prompts):
+                    hist[i], hn[i] = ring_of(p, W)
+                _upload(g.hist, hist)
+                _upload(g.hist_n, hn)
+                g.last_n.fill_(params.repeat_last_n)
+                g.rep_pen.fill_(params.repeat_penalty)
+                g.pres_pen.fill_(params.presence_penalty)
+                g.freq_pen.fill_(params.frequency_penalty)
+                first = self._penalized_greedy(logits, g) if greedy else self._select(logits, g)
+                rows = torch.arange(B, device=dev)
+                g.hist[rows, (g.hist_n[:B] % W).long()] = first.int()
+                g.hist_n[:B] += 1
+            else:
+                first = logits if greedy else self._select(logits, g)
             gen = torch.empty(B, params.max_new_tokens, dtype=torch.long, device=dev)
             gen[:, 0] = first
             tok = torch.zeros(g.bp, dtype=torch.int32, device=dev)

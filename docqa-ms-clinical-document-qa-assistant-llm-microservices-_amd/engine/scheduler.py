@@ -61,7 +61,7 @@ from .. import ops
 from ..parallel import comm
 from ..parallel.custom_ar import CollectiveError
 from ..utils import tracing
-from .llm_engine import LLMEngine, SamplingParams, _bucket, _DecodeGraph, _prefill_inputs
+from .llm_engine import LLMEngine, SamplingParams, _bucket, _DecodeGraph, _prefill_inputs, ring_of
 
 
 @dataclass
@@ -71,6 +71,7 @@ class Request:
     params: SamplingParams
     future: cf.Future
     on_token: object = None          # callable(rid, token) for streaming
+    stop_check: object = None        # callable(list[int]) -> bool on the output so far (stop strings)
     out: list[int] = field(default_factory=list)
     blocks: list[int] = field(default_factory=list)
     cached: int = 0
@@ -166,14 +167,24 @@ class ContinuousEngine:
         self.mixed_steps = 0
 
     # ------------------------------------------------------------------ client side
-    def submit(self, prompt: list[int], params: SamplingParams | None = None, on_token=None) -> cf.Future:
+    def submit(self, prompt: list[int], params: SamplingParams | None = None, on_token=None,
+               stop_check=None) -> cf.Future:
+        """``stop_check(out)``: called with the request's generated ids after each emitted
+        token; a true result finishes the request there (stop strings -- the caller owns the
+        tokenizer).  A check that raises is dropped, like ``on_token``."""
         params = params or SamplingParams()
         fut: cf.Future = cf.Future()
         if len(prompt) + params.max_new_tokens > self.eng.max_context or not prompt:
             fut.set_exception(ValueError(
                 f"prompt+generation {len(prompt) + params.max_new_tokens} exceeds max_context {self.eng.max_context}"))
             return fut
-        r = Request(next(self._ids), list(prompt), params, fut, on_token, t_arrival=time.perf_counter())
+        if self.lockstep is not None:
+            # a host callable cannot be mirrored on the followers, and retiring a row on the
+            # leader alone would break the lockstep: the request runs to EOS / its token limit
+            # (the API layer truncates the text at the stop string all the same)
+            stop_check = None
+        r = Request(next(self._ids), list(prompt), params, fut, on_token, stop_check,
+                    t_arrival=time.perf_counter())
         with self._cv:
             # a lockstep leader queues arrivals for the next step's broadcast, so the
             # followers see exactly the waiting queue its admission sees
@@ -192,9 +203,9 @@ class ContinuousEngine:
         return [f.result() for f in futs]
 
     @torch.inference_mode()
-    def warmup(self, buckets: list[int] | None = None, sampled: bool = False) -> None:
+    def warmup(self, buckets: list[int] | None = None, sampled: bool = False, penalized: bool = False) -> None:
         """Capture the decode graphs of every bucket (plain and cascade; greedy, and
-        sampled if asked) before serving, so no request pays a capture / GEMM-tuning
+        sampled if asked; their penalised flavours too if asked) before serving, so no request pays a capture / GEMM-tuning
         stall mid-stream.  Slots are empty (valid 0): the captured warm-up steps write
         nothing to the KV cache."""
         if not self.eng.use_graphs or self.running:
@@ -208,11 +219,12 @@ class ContinuousEngine:
         for bp in buckets or bs:
             for greedy in ([True, False] if sampled else [True]):
                 for c in casc:
-                    g = self._graph(bp, greedy, c)
-                    if g.graph is None:
-                        if self._pool is None:
-                            self._pool = torch.cuda.graph_pool_handle()
-                        self.eng._capture(g, self._pool)
+                    for pen in ([False, True] if penalized else [False]):
+                        g = self._graph(bp, greedy, c, penalized=pen)
+                        if g.graph is None:
+                            if self._pool is None:
+                                self._pool = torch.cuda.graph_pool_handle()
+                            self.eng._capture(g, self._pool)
 
     # ------------------------------------------------------------------ serving thread
     def start(self) -> "ContinuousEngine":
@@ -357,14 +369,14 @@ class ContinuousEngine:
 
     def _take_waiting(self, mixed: bool = False, token_cap: int | None = None) -> list[Request]:
         """Reserve KV blocks for waiting requests while slots are free.  ``mixed``: for the
-        chunked-prefill queue -- greedy requests only (a sampled one waits for a plain
-        admission), and stop once ``token_cap`` prompt tokens are taken."""
+        chunked-prefill queue -- unpenalised greedy requests only (a sampled or penalised one
+        waits for a plain admission), and stop once ``token_cap`` prompt tokens are taken."""
         eng, alloc = self.eng, self.eng.kv.allocator
         admitted, budget = [], 0
         with self._cv:
             while self.waiting and self._occupied() + len(admitted) < self.max_running:
                 r = self.waiting[0]
-                if mixed and (r.params.temperature > 0 or (token_cap is not None and budget >= token_cap)):
+                if mixed and (not r.params.fused_greedy_ok or (token_cap is not None and budget >= token_cap)):
                     break
                 if r.orig_len < 0:
                     r.orig_len = len(r.prompt)
@@ -437,11 +449,12 @@ class ContinuousEngine:
             with tracing.span("sched.admit", seqs=len(adm), tokens=sum(len(r.prompt) - r.cached for r in adm)):
                 for r in adm:
                     eng.queue_prefix_copies(r.res)
-                greedy = all(r.params.temperature <= 0 for r in adm)
+                greedy = all(r.params.fused_greedy_ok for r in adm)
                 out = eng._prefill([r.prompt for r in adm], [r.blocks for r in adm], [r.cached for r in adm],
                                    greedy=greedy)
                 err = comm.collective_error_snapshot()
-                first = out.tolist() if greedy else self._sample_rows(out, [r.params for r in adm])
+                first = out.tolist() if greedy else self._sample_rows(out, [r.params for r in adm],
+                                                                          [self._stream(r) for r in adm])
                 comm.raise_on_collective_error(err)
         except CollectiveError:
             for r in adm:
@@ -485,8 +498,8 @@ class ContinuousEngine:
             return False
         if self.prefilling:
             return True
-        due = bool(self.running and self.waiting and self.waiting[0].params.temperature <= 0
-                   and all(r.params.temperature <= 0 for r in self.running))
+        due = bool(self.running and self.waiting and self.waiting[0].params.fused_greedy_ok
+                   and all(r.params.fused_greedy_ok for r in self.running))
         if due and self.mixed_hold:
             due = self._admission_due() if decision is None else bool(decision)
         return due
@@ -655,7 +668,18 @@ class ContinuousEngine:
         it = torch.ones(k, dtype=torch.float32)
         tk = torch.zeros(k, dtype=torch.int32)
         tp = torch.ones(k, dtype=torch.float32)
+        # penalties: the ring is the tail of the request's stream so far, first token included
+        W = ops.PENALTY_WINDOW
+        hist = torch.zeros(k, W, dtype=torch.int32)
+        hn = torch.zeros(k, dtype=torch.int32)
+        ln = torch.zeros(k, dtype=torch.int32)
+        pen = torch.tensor([[1.0, 0.0, 0.0]] * k, dtype=torch.float32)
         for i, r in enumerate(reqs):
+            if not r.params.neutral:
+                hist[i], hn[i] = ring_of(self._stream(r), W)
+                ln[i] = r.params.repeat_last_n
+                pen[i] = torch.tensor([r.params.repeat_penalty, r.params.presence_penalty,
+                                       r.params.frequency_penalty])
             bt[i, :len(r.blocks)] = torch.tensor(r.blocks, dtype=torch.int32)
             tok[i] = r.out[-1]
             # the input of the next step sits right after the prompt (+ tokens generated since
@@ -676,28 +700,62 @@ class ContinuousEngine:
         m.inv_temp[sl].copy_(it.to(dev, non_blocking=True))
         m.top_k[sl].copy_(tk.to(dev, non_blocking=True))
         m.top_p[sl].copy_(tp.to(dev, non_blocking=True))
+        m.hist[sl].copy_(hist.to(dev, non_blocking=True))
+        m.hist_n[sl].copy_(hn.to(dev, non_blocking=True))
+        m.last_n[sl].copy_(ln.to(dev, non_blocking=True))
+        m.rep_pen[sl].copy_(pen[:, 0].contiguous().to(dev, non_blocking=True))
+        m.pres_pen[sl].copy_(pen[:, 1].contiguous().to(dev, non_blocking=True))
+        m.freq_pen[sl].copy_(pen[:, 2].contiguous().to(dev, non_blocking=True))
         self.running.extend(reqs)
         self._version += 1
 
-    def _sample_rows(self, logits: torch.Tensor, params: list[SamplingParams]) -> list[int]:
+    @staticmethod
+    def _stream(r: Request) -> list[int]:
+        """Prompt + output so far (a resumed prompt already holds the first ``gen_base``
+        output tokens: only the original prompt counts)."""
+        return r.prompt[:r.orig_len if r.orig_len >= 0 else len(r.prompt)] + r.out
+
+    def _sample_rows(self, logits: torch.Tensor, params: list[SamplingParams],
+                     streams: list[list[int]] | None = None) -> list[int]:
+        """First tokens of admitted requests from their prefill logits; ``streams``: each
+        request's tokens so far, the penalty window of the penalised ones."""
         model = self.eng.model
-        if all(p.temperature <= 0 for p in params):
+        if all(p.fused_greedy_ok for p in params):
             return model.greedy(logits).tolist()
-        full = model.full_logits(logits).float()
+        full = model.full_logits(logits)
         dev = full.device
+        pen = None
+        if not all(p.neutral for p in params):
+            W = ops.PENALTY_WINDOW
+            rings = [ring_of(s if not p.neutral else [], W) for p, s in zip(params, streams)]
+            pen = (torch.stack([h for h, _ in rings]).to(dev),
+                   torch.tensor([n for _, n in rings], dtype=torch.int32, device=dev),
+                   torch.tensor([p.repeat_last_n for p in params], dtype=torch.int32, device=dev),
+                   torch.tensor([p.repeat_penalty for p in params], dtype=torch.float32, device=dev),
+                   torch.tensor([p.presence_penalty for p in params], dtype=torch.float32, device=dev),
+                   torch.tensor([p.frequency_penalty for p in params], dtype=torch.float32, device=dev))
+            if all(p.temperature <= 0 for p in params):
+                return ops.penalized_argmax(full, full.shape[1], *pen).tolist()
+        if pen is not None and (full.dtype == torch.float32):
+            full = full.clone(memory_format=torch.contiguous_format)
+        full = full.float()
+        if pen is not None:
+            ops.apply_penalties(full, *pen)
         it = torch.tensor([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in params], device=dev)
         tk = torch.tensor([p.top_k if p.temperature > 0 else 1 for p in params], dtype=torch.int32, device=dev)
         tp = torch.tensor([p.top_p if p.temperature > 0 else 1.0 for p in params], device=dev)
         u = torch.rand(full.shape[0], device=dev)
         return ops.sample(full, it, tk, tp, u).tolist()
 
-    def _graph(self, bp: int, greedy: bool, cascade: bool, fit: bool = True) -> _DecodeGraph:
+    def _graph(self, bp: int, greedy: bool, cascade: bool, fit: bool = True,
+               penalized: bool = False) -> _DecodeGraph:
         fit = fit or self._master.groups_fit
-        key = (bp, greedy, cascade, fit)
+        key = (bp, greedy, cascade, fit, penalized)
         g = self._graphs.get(key)
         if g is None:
             g = _DecodeGraph.view_of(self._master, bp)
             g.greedy, g.cascade, g.groups_fit = greedy, cascade, fit
+            g.penalized = penalized
             self._graphs[key] = g
         return g
 
@@ -787,9 +845,10 @@ class ContinuousEngine:
             return
         bp = _bucket(n, eng.max_batch) if self.pad_buckets else n
         greedy = all(r.params.temperature <= 0 for r in self.running)
+        penalized = not all(r.params.neutral for r in self.running)
         fit = self._groups_fit()
         grouped = self._nshared > 0 or eng.group_without_prefix(n, fit)
-        g = self._graph(bp, greedy, grouped, fit)
+        g = self._graph(bp, greedy, grouped, fit, penalized)
         if eng.lpt:
             # re-rank only when the running set changed (admission / retirement)
             eng.set_order(g, [len(r.prompt) + len(r.out) for r in self.running], key=self._version)
@@ -876,7 +935,14 @@ class ContinuousEngine:
     def _finished(self, r: Request) -> bool:
         if len(r.out) >= r.params.max_new_tokens:
             return True
-        return r.params.stop_on_eos and r.out[-1] == self.eng.cfg.eos_token_id
+        if r.params.stop_on_eos and r.out[-1] == self.eng.cfg.eos_token_id:
+            return True
+        if r.stop_check is not None:
+            try:
+                return bool(r.stop_check(list(r.out)))
+            except Exception:  # noqa: BLE001 - a client callback must not stop the engine
+                r.stop_check = None
+        return False
 
     def _retire(self, r: Request) -> None:
         self.completed += 1
@@ -892,7 +958,7 @@ class ContinuousEngine:
         if keep != list(range(k)):
             idx = torch.tensor(keep, dtype=torch.long, device=m.tokens.device)
             for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
-                         "top_k", "top_p"):
+                         "top_k", "top_p", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen"):
                 t = getattr(m, name)
                 t[:k] = t[idx]
         m.valid[k:n].zero_()

@@ -1005,6 +1005,41 @@ def sample(logits, inv_temp, top_k, top_p, u):
     return ref.sample(logits, inv_temp, top_k, top_p, u)
 
 
+PENALTY_WINDOW = ref.PENALTY_WINDOW   # capacity W of the per-slot token ring hist [B, W]
+
+
+def apply_penalties(logits, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid=None) -> None:
+    """In place on fp32 logits [R, V]: llama.cpp's repeat / presence / frequency penalties over
+    each row's newest min(hist_n, last_n, W) ring tokens -- per distinct token t with count c,
+    l = l <= 0 ? l * rp : l / rp, then l -= c * fp + pp (fp32, each operation rounded on its
+    own: GPU and reference agree bitwise).  Neutral rows (rp 1, pp 0, fp 0, or last_n 0) and
+    rows with valid 0 are left untouched."""
+    if _gpu(logits):
+        _native().apply_penalties(logits, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid)
+        return
+    ref.apply_penalties(logits, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid)
+
+
+def penalized_argmax(logits, n_valid: int, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid=None):
+    """Greedy pick under the penalties of :func:`apply_penalties`: int64 [R], the argmax over
+    t < n_valid of the penalised bf16 / fp32 logits [R, V], ties to the lowest index.  On a GPU
+    the logits are read once, no fp32 copy is made and ``logits`` is CLOBBERED (the window
+    tokens' entries are overwritten); logits are expected to be finite."""
+    if _gpu(logits):
+        return _native().penalized_argmax(logits, int(n_valid), hist, hist_n, last_n, rep_pen, pres_pen,
+                                          freq_pen, valid)
+    return ref.penalized_argmax(logits, n_valid, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid)
+
+
+def decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n) -> None:
+    """:func:`decode_advance`, and the valid rows' new token joins their ring:
+    hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1."""
+    if _gpu(nxt):
+        _native().decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n)
+        return
+    ref.decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n)
+
+
 # ----------------------------------------------------------------------------- attention
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, Hq, max_context, scale, order=None):
     """``order``: optional int32 permutation of the rows -- the workgroup dispatch order

@@ -367,6 +367,76 @@ def decode_advance(nxt, out, tokens, positions, context_lens, valid) -> None:
     context_lens.add_(valid)
 
 
+PENALTY_WINDOW = 256   # ring capacity W of the token history (embed_sample.hip kPenaltyWindow)
+
+
+def penalty_neutral(last_n: int, rp: float, pp: float, fp: float) -> bool:
+    return last_n == 0 or (rp == 1.0 and pp == 0.0 and fp == 0.0)
+
+
+def _window_counts(hist_row, hist_n: int, last_n: int, V: int) -> dict:
+    """{token: count} over the newest min(hist_n, last_n, W) ring entries (stream entry j sits
+    at hist_row[j % W]; last_n < 0 or above W means W); ids outside [0, V) are ignored."""
+    W = hist_row.numel()
+    n = max(0, min(hist_n, W))
+    if 0 <= last_n < n:
+        n = last_n
+    ring = hist_row.tolist()
+    counts: dict = {}
+    for j in range(hist_n - n, hist_n):
+        t = ring[j % W]
+        if 0 <= t < V:
+            counts[t] = counts.get(t, 0) + 1
+    return counts
+
+
+def _penalize_row(x, counts: dict, rp, pp, fp) -> None:
+    """In place on the fp32 row ``x``; rp / pp / fp are fp32 0-d tensors.  Every operation is
+    rounded to fp32 on its own, in the kernels' order: l = l <= 0 ? l * rp : l / rp, then
+    l = l - (c * fp + pp)."""
+    for t, c in counts.items():
+        l = x[t]
+        l = l * rp if bool(l <= 0) else l / rp
+        x[t] = l - (torch.tensor(float(c), dtype=torch.float32) * fp + pp)
+
+
+def _row_params(r, hist_n, last_n, rep_pen, pres_pen, freq_pen):
+    f32 = lambda v: v[r].detach().to("cpu", torch.float32)   # noqa: E731
+    return int(hist_n[r]), int(last_n[r]), f32(rep_pen), f32(pres_pen), f32(freq_pen)
+
+
+def apply_penalties(logits, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid=None) -> None:
+    """llama.cpp's repeat / presence / frequency penalties, in place on fp32 logits [R, V]."""
+    assert logits.dtype == torch.float32
+    V = logits.shape[1]
+    for r in range(logits.shape[0]):
+        hn, ln, rp, pp, fp = _row_params(r, hist_n, last_n, rep_pen, pres_pen, freq_pen)
+        if (valid is not None and int(valid[r]) == 0) or penalty_neutral(ln, float(rp), float(pp), float(fp)):
+            continue
+        counts = _window_counts(hist[r].cpu(), hn, ln, V)
+        if counts:
+            idx = torch.tensor(list(counts), dtype=torch.long)
+            x = logits[r, idx].cpu()
+            _penalize_row(x, {i: c for i, c in enumerate(counts.values())}, rp, pp, fp)
+            logits[r, idx.to(logits.device)] = x.to(logits.device)
+
+
+def penalized_argmax(logits, n_valid: int, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid=None):
+    """argmax over t < n_valid of the penalised logits (unpenalised entries as float(logit)),
+    ties to the lowest index; the input is left unchanged here."""
+    x = logits[:, :n_valid].float().clone()
+    apply_penalties(x, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid)
+    return x.argmax(dim=-1)
+
+
+def decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n) -> None:
+    W = hist.shape[1]
+    rows = torch.nonzero(valid.bool())[:, 0]
+    hist[rows, (hist_n[rows] % W).long()] = nxt[rows].int()
+    hist_n.add_(valid)
+    decode_advance(nxt, out, tokens, positions, context_lens, valid)
+
+
 def coarse_probes(xq, centroids, cnorm, nprobe: int):
     """fp32 reference of csrc/kernels/coarse.hip: ||c||^2 - 2 q.c per (query, centroid),
     the nprobe smallest in ascending order, ties to the lower centroid id (stable sort)."""

@@ -163,7 +163,11 @@ def run_parallel(a, opts: "StackOptions") -> None:
                         kv_mem_fraction=opts.kv_mem_fraction)
         ce = ContinuousEngine(eng, max_running=st.max_batch, lockstep=ls)
         if os.environ.get("DOCQA_WARM_BUCKETS", "1") == "1":
-            ce.warmup()        # the leader captures the same buckets in the same order (qa.py)
+            from ..engine.llm_engine import SamplingParams
+            from .qa import penalty_defaults
+
+            # the leader captures the same buckets in the same order (qa.py)
+            ce.warmup(penalized=not SamplingParams(**penalty_defaults(st)).neutral)
         print(f"[rank {ps.rank}] TP follower of group {ps.dp_rank} ready", flush=True)
         ce.follow()
         comm.destroy()

@@ -9,7 +9,9 @@ service's URL gets its completions from the MI355X engine (continuous batching w
 other request in flight) instead of a llama.cpp process.
 
   POST /api/chat      {"model", "messages": [{"role", "content"}], "stream" (default true),
-                       "options": {"temperature", "num_predict", "top_k", "top_p", "seed"}}
+                       "options": {"temperature", "num_predict", "top_k", "top_p", "seed",
+                                   "repeat_penalty", "repeat_last_n", "presence_penalty",
+                                   "frequency_penalty", "stop"}}
                       -> {"model", "created_at", "message": {"role": "assistant", "content"},
                           "done": true, "done_reason": "stop" | "length", "total_duration",
                           "load_duration", "prompt_eval_count", "prompt_eval_duration",
@@ -23,7 +25,11 @@ other request in flight) instead of a llama.cpp process.
 
 Deviations, by design: one model per process (the request's "model" is echoed, not used to
 pick weights); "temperature" defaults to the service's TEMPERATURE (0, the reference's
-setting) rather than Ollama's 0.8; "format", "keep_alive", "images" and "tools" are ignored.
+setting) rather than Ollama's 0.8, and the penalties to the service's neutral REPEAT_PENALTY /
+REPEAT_LAST_N / PRESENCE_PENALTY / FREQUENCY_PENALTY rather than Ollama's 1.1 over 64 tokens
+(docs/CONFIG.md); "format", "keep_alive", "images" and "tools" are ignored.  "stop" (a string
+or a list) ends the text just before the earliest match with done_reason "stop"; a streamed
+tail that could still grow into a stop string is held back until it is resolved.
 Durations are nanoseconds like Ollama's.  Streaming is token by token on the continuous
 scheduler (DOCQA_SERVING=continuous, the default); the static batcher returns the whole
 completion as one piece.
@@ -71,14 +77,49 @@ def _now() -> str:
 
 def sampling_from_options(options: dict | None, settings, max_context: int, prompt_len: int) -> SamplingParams:
     """Ollama ``options`` -> SamplingParams: num_predict (-1 / -2: up to the context) caps
-    the new tokens, temperature 0 is greedy."""
+    the new tokens, temperature 0 is greedy; the penalties default to the service settings."""
     o = options or {}
     n = int(o.get("num_predict", settings.max_new_tokens))
     room = max(1, max_context - prompt_len)
     n = room if n < 0 else max(1, min(n, room))
     return SamplingParams(max_new_tokens=n, temperature=float(o.get("temperature", settings.temperature)),
                           top_k=int(o.get("top_k", 0) or 0), top_p=float(o.get("top_p", 1.0) or 1.0),
-                          stop_on_eos=True, seed=int(o.get("seed", 0) or 0))
+                          stop_on_eos=True, seed=int(o.get("seed", 0) or 0),
+                          repeat_penalty=float(_opt(o, "repeat_penalty", settings.repeat_penalty)),
+                          repeat_last_n=int(_opt(o, "repeat_last_n", settings.repeat_last_n)),
+                          presence_penalty=float(_opt(o, "presence_penalty", settings.presence_penalty)),
+                          frequency_penalty=float(_opt(o, "frequency_penalty", settings.frequency_penalty)))
+
+
+def _opt(o: dict, name: str, default):
+    v = o.get(name)
+    return default if v is None else v
+
+
+def stop_strings(options: dict | None) -> list[str]:
+    """``options.stop``: a string or a list of strings (empty ones dropped)."""
+    s = (options or {}).get("stop")
+    if isinstance(s, str):
+        s = [s]
+    return [x for x in (s or []) if isinstance(x, str) and x]
+
+
+def find_stop(text: str, stops: list[str]) -> int:
+    """Index of the earliest occurrence of any stop string in ``text``, -1 if none."""
+    hits = [i for i in (text.find(s) for s in stops) if i >= 0]
+    return min(hits) if hits else -1
+
+
+def held_back(text: str, stops: list[str]) -> int:
+    """Length of the longest tail of ``text`` that is a proper prefix of a stop string: it
+    may still grow into one, so a stream does not send it yet."""
+    best = 0
+    for s in stops:
+        for k in range(min(len(s) - 1, len(text)), best, -1):
+            if text.endswith(s[:k]):
+                best = k
+                break
+    return best
 
 
 def register(app: FastAPI, settings, metrics) -> None:
@@ -106,7 +147,12 @@ def register(app: FastAPI, settings, metrics) -> None:
                 first[0] = time.perf_counter()
             loop.call_soon_threadsafe(q.put_nowait, t)
 
-        fut = batcher.submit("gen", {"ids": ids, "params": params, "on_token": on_token if stream else None})
+        stops = stop_strings(options)
+        # the scheduler retires the request at the token that completes a stop string (the
+        # static batcher has no per-token hook: it runs to num_predict, the text is cut below)
+        stop_check = (lambda out: find_stop(tok.decode(out), stops) >= 0) if stops else None
+        fut = batcher.submit("gen", {"ids": ids, "params": params, "on_token": on_token if stream else None,
+                                     "stop_check": stop_check})
         fut.add_done_callback(lambda f: loop.call_soon_threadsafe(q.put_nowait, _DONE))
 
         def body(text: str) -> dict:
@@ -114,12 +160,16 @@ def register(app: FastAPI, settings, metrics) -> None:
                 return {"message": {"role": "assistant", "content": text}}
             return {"response": text}
 
-        def final(out: list[int], text: str) -> dict:
+        def cut(text: str) -> tuple[str, bool]:
+            i = find_stop(text, stops) if stops else -1
+            return (text[:i], True) if i >= 0 else (text, False)
+
+        def final(out: list[int], text: str, stopped: bool = False) -> dict:
             t1 = time.perf_counter()
             tf = first[0] or t1
             eos = bool(out) and out[-1] == pipe.engine.model.cfg.eos_token_id
             d = {"model": model or settings.llm_model, "created_at": _now(), **body(text), "done": True,
-                 "done_reason": "stop" if eos else "length", "total_duration": int((t1 - t0) * 1e9),
+                 "done_reason": "stop" if eos or stopped else "length", "total_duration": int((t1 - t0) * 1e9),
                  "load_duration": 0, "prompt_eval_count": len(ids), "prompt_eval_duration": int((tf - t0) * 1e9),
                  "eval_count": len(out), "eval_duration": int((t1 - tf) * 1e9)}
             if kind == "generate":
@@ -128,7 +178,8 @@ def register(app: FastAPI, settings, metrics) -> None:
 
         if not stream:
             res = await asyncio.wrap_future(fut)
-            return JSONResponse(final(res["ids"], tok.decode(res["ids"])))
+            text, stopped = cut(tok.decode(res["ids"]))
+            return JSONResponse(final(res["ids"], text, stopped))
 
         async def lines():
             got: list[int] = []
@@ -141,6 +192,12 @@ def register(app: FastAPI, settings, metrics) -> None:
                 text = tok.decode(got)
                 if text.endswith("\ufffd"):     # an incomplete UTF-8 sequence: wait for its bytes
                     continue
+                if stops:
+                    text, stopped = cut(text)
+                    if not stopped:
+                        text = text[:len(text) - held_back(text, stops)]
+                    if len(text) < len(sent) or not text.startswith(sent):
+                        continue
                 piece, sent = text[len(sent):], text
                 if piece:
                     yield json.dumps({"model": model or settings.llm_model, "created_at": _now(), **body(piece),
@@ -150,12 +207,12 @@ def register(app: FastAPI, settings, metrics) -> None:
             except Exception as e:  # noqa: BLE001 - the stream is already open: report in-band
                 yield json.dumps({"error": f"{type(e).__name__}: {e}"}) + "\n"
                 return
-            text = tok.decode(out)
+            text, stopped = cut(tok.decode(out))
             rest = text[len(sent):] if text.startswith(sent) else text
             if rest:     # the static batcher (no per-token callback) or a held-back tail
                 yield json.dumps({"model": model or settings.llm_model, "created_at": _now(), **body(rest),
                                   "done": False}) + "\n"
-            yield json.dumps(final(out, "")) + "\n"
+            yield json.dumps(final(out, "", stopped)) + "\n"
 
         return StreamingResponse(lines(), media_type="application/x-ndjson")
 

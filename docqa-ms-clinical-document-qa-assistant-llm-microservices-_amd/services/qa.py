@@ -40,6 +40,13 @@ from ..utils import tracing
 from ..utils.metrics import Metrics
 
 
+def penalty_defaults(st: Settings) -> dict:
+    """The service-wide penalty settings (REPEAT_PENALTY / REPEAT_LAST_N / PRESENCE_PENALTY /
+    FREQUENCY_PENALTY) as SamplingParams fields."""
+    return {"repeat_penalty": st.repeat_penalty, "repeat_last_n": st.repeat_last_n,
+            "presence_penalty": st.presence_penalty, "frequency_penalty": st.frequency_penalty}
+
+
 class DynamicBatcher:
     def __init__(self, pipeline, settings: Settings, metrics: Metrics):
         self.pipe = pipeline
@@ -57,7 +64,7 @@ class DynamicBatcher:
 
     def _params(self) -> SamplingParams:
         return SamplingParams(max_new_tokens=self.st.max_new_tokens, temperature=self.st.temperature,
-                              stop_on_eos=self.st.stop_on_eos)
+                              stop_on_eos=self.st.stop_on_eos, **penalty_defaults(self.st))
 
     def _loop(self) -> None:
         while not self._stop.is_set():
@@ -95,7 +102,8 @@ class DynamicBatcher:
             groups: dict = {}
             for b in gens:
                 p = b[1]["params"]
-                groups.setdefault((p.max_new_tokens, p.temperature, p.top_k, p.top_p, p.stop_on_eos, p.seed),
+                groups.setdefault((p.max_new_tokens, p.temperature, p.top_k, p.top_p, p.stop_on_eos, p.seed,
+                                   p.repeat_penalty, p.repeat_last_n, p.presence_penalty, p.frequency_penalty),
                                   []).append(b)
             for grp in groups.values():
                 outs = self.pipe.engine.generate([b[1]["ids"] for b in grp], grp[0][1]["params"])
@@ -154,7 +162,7 @@ class ContinuousBatcher:
         if os.environ.get("DOCQA_WARM_BUCKETS", "1") == "1":
             # every decode bucket captured before the first request (the TP followers do
             # the same before following, services/launch.py)
-            self.engine.warmup()
+            self.engine.warmup(penalized=not self._params().neutral)
         self.q: queue.Queue = queue.Queue()
         self._prep_window_s = float(os.environ.get("DOCQA_PREP_WINDOW_MS", "0")) / 1e3
         self._stop = threading.Event()
@@ -170,7 +178,7 @@ class ContinuousBatcher:
 
     def _params(self) -> SamplingParams:
         return SamplingParams(max_new_tokens=self.st.max_new_tokens, temperature=self.st.temperature,
-                              stop_on_eos=self.st.stop_on_eos)
+                              stop_on_eos=self.st.stop_on_eos, **penalty_defaults(self.st))
 
     def _drain(self) -> list:
         """Everything queued now; while the engine is busy, also what arrives within
@@ -291,7 +299,8 @@ class ContinuousBatcher:
                 self.metrics.observe("generate_latency_s", time.perf_counter() - t0)
                 f.set_result({"ids": list(ef.result())})
 
-            self.engine.submit(g["ids"], g["params"], g.get("on_token")).add_done_callback(gdone)
+            self.engine.submit(g["ids"], g["params"], g.get("on_token"),
+                               g.get("stop_check")).add_done_callback(gdone)
         for _, text, f, t0 in sums:
             p = pipe.chat_tok.chat_prompt(text)
             lim = pipe.max_prompt_tokens
