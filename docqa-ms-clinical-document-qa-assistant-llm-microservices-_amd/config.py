@@ -87,6 +87,9 @@ class Settings:
     # generator weight format: bf16 | fp8 (per-row e4m3 copies streamed by one-row decode steps,
     # models/llama.py quantize_fp8; read by models/checkpoint.py resolve_llama)
     llm_weights: str = field(default_factory=lambda: os.getenv("DOCQA_LLM_WEIGHTS", "bf16"))
+    # paged KV cache format: bf16 | fp8 (e4m3 codes without scales: half the bytes per block;
+    # read by engine/llm_engine.py LLMEngine(kv_dtype=None))
+    kv_cache: str = field(default_factory=lambda: os.getenv("DOCQA_KV_CACHE", "bf16"))
     top_k: int = field(default_factory=lambda: env_int("TOP_K", 3))
     max_new_tokens: int = field(default_factory=lambda: env_int("MAX_NEW_TOKENS", 256))
     temperature: float = field(default_factory=lambda: float(os.getenv("TEMPERATURE", "0")))

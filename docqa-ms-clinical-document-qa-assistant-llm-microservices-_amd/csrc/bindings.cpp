@@ -90,6 +90,24 @@ at::Tensor layernorm(const at::Tensor& x, const c10::optional<at::Tensor>& resid
   return out;
 }
 
+// Paged KV dtype of the entry points that implement the FP8 cache (OCP e4m3 codes, no scales,
+// [num_blocks, Hkv, BS, D] like the bf16 pools): true for an FP8 pair, false for bf16, anything
+// else -- or a mixed pair -- is refused.  Every other entry point keeps CHECK_BF16 on its
+// caches: a dtype an entry point does not implement fails, bytes are never reinterpreted.
+static bool kv_fp8(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t Hkv, int64_t D) {
+  if (k_cache.scalar_type() != at::kFloat8_e4m3fn) {
+    CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+    return false;
+  }
+  TORCH_CHECK(v_cache.scalar_type() == at::kFloat8_e4m3fn, "k_cache and v_cache must have one dtype");
+  CHECK_GPU(k_cache); CHECK_GPU(v_cache); CHECK_CONTIG(k_cache); CHECK_CONTIG(v_cache);
+  CHECK_ALIGN16(k_cache); CHECK_ALIGN16(v_cache);
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() && k_cache.size(1) == Hkv &&
+                  k_cache.size(3) == D, "FP8 KV cache: [num_blocks, Hkv, BS, D]");
+  TORCH_CHECK(D == 128 && k_cache.size(2) == 64, "FP8 KV cache: head_dim 128 and 64-token blocks");
+  return true;
+}
+
 void rope_cache(at::Tensor qkv, const at::Tensor& positions, const at::Tensor& cos_sin,
                 const c10::optional<at::Tensor>& slot_mapping, at::Tensor k_cache,
                 at::Tensor v_cache, int64_t Hq, int64_t Hkv, int64_t D) {
@@ -103,7 +121,14 @@ void rope_cache(at::Tensor qkv, const at::Tensor& positions, const at::Tensor& c
   if (slot_mapping.has_value()) {
     CHECK_I32(*slot_mapping);
     sm = slot_mapping->data_ptr<int>();
-    CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+    if (kv_fp8(k_cache, v_cache, Hkv, D)) {
+      CHECK_ALIGN16(qkv);
+      c10::DeviceGuard g8(qkv.device());
+      CHECK_RC(docqa_rope_cache8(qkv.data_ptr(), positions.data_ptr<int>(), cos_sin.data_ptr<float>(), sm,
+                                 k_cache.data_ptr(), v_cache.data_ptr(), T, Hq, Hkv, D, qkv.size(-1),
+                                 k_cache.size(2), stream()), "rope_cache (fp8 cache)");
+      return;
+    }
     BS = k_cache.size(2);  // [num_blocks, Hkv, BS, D]
   }
   c10::DeviceGuard g(qkv.device());
@@ -125,6 +150,19 @@ void kv_copy_rows(const at::Tensor& caches, const at::Tensor& tab, int64_t num_b
                               tab.data_ptr<int>(), (int)tab.size(0), (int)num_blocks, (int)Hkv, (int)BS, (int)D,
                               stream()),
            "kv_copy_rows");
+}
+
+// the same for FP8 pools (1-byte elements; the addresses carry no dtype, so the caller picks)
+void kv_copy_rows8(const at::Tensor& caches, const at::Tensor& tab, int64_t num_blocks, int64_t Hkv, int64_t BS,
+                   int64_t D) {
+  CHECK_GPU(caches); CHECK_GPU(tab); CHECK_I32(tab); CHECK_CONTIG(tab); CHECK_CONTIG(caches);
+  TORCH_CHECK(caches.scalar_type() == at::kLong && caches.dim() == 1, "caches: int64 [2 L] addresses");
+  TORCH_CHECK(tab.dim() == 2 && tab.size(1) == 3, "tab: [n, 3] (src, dst, rows)");
+  c10::DeviceGuard g(tab.device());
+  CHECK_RC(docqa_kv_copy_rows8(reinterpret_cast<const uint64_t*>(caches.data_ptr<int64_t>()), (int)caches.numel(),
+                               tab.data_ptr<int>(), (int)tab.size(0), (int)num_blocks, (int)Hkv, (int)BS, (int)D,
+                               stream()),
+           "kv_copy_rows8");
 }
 
 // split-K partial slabs P [S, rows, H] fp32 -> residual += bf16(sum P); rmsnorm(residual) * w
@@ -159,14 +197,22 @@ at::Tensor rope_cache_splitk(const at::Tensor& P, const at::Tensor& positions, c
   const int T = P.size(1);
   const int* sm = nullptr;
   int BS = 1;
+  bool f8 = false;
   if (slot_mapping.has_value()) {
     CHECK_I32(*slot_mapping);
     sm = slot_mapping->data_ptr<int>();
-    CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+    f8 = kv_fp8(k_cache, v_cache, Hkv, D);
     BS = k_cache.size(2);
   }
   c10::DeviceGuard g(P.device());
   auto qkv = at::empty({T, P.size(2)}, P.options().dtype(at::kBFloat16));
+  if (f8) {   // codes to the cache, their bf16 image to qkv
+    CHECK_RC(docqa_rope_cache_splitk8(P.data_ptr(), P.scalar_type() == at::kBFloat16, P.size(0), qkv.data_ptr(),
+                                      positions.data_ptr<int>(), cos_sin.data_ptr<float>(), sm, k_cache.data_ptr(),
+                                      v_cache.data_ptr(), T, Hq, Hkv, D, P.size(2), BS, stream()),
+             "rope_cache_splitk (fp8 cache)");
+    return qkv;
+  }
   if (P.scalar_type() == at::kBFloat16)
     CHECK_RC(docqa_rope_cache_splitk16(P.data_ptr(), P.size(0), qkv.data_ptr(), positions.data_ptr<int>(),
                                        cos_sin.data_ptr<float>(), sm, sm ? k_cache.data_ptr() : nullptr,
@@ -477,7 +523,9 @@ at::Tensor paged_decode(const at::Tensor& q, const at::Tensor& k_cache, const at
                         int64_t Hq, int64_t max_context, double scale,
                         const c10::optional<at::Tensor>& order) {
   // q: [B, >= Hq*D] rows (e.g. the packed QKV buffer), caches [NB, Hkv, BS, D]
-  CHECK_GPU(q); CHECK_BF16(q); CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+  CHECK_GPU(q); CHECK_BF16(q);
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache: [num_blocks, Hkv, BS, D]");
+  const bool f8 = kv_fp8(k_cache, v_cache, k_cache.size(1), k_cache.size(3));
   CHECK_I32(block_tables); CHECK_I32(context_lens); CHECK_CONTIG(block_tables);
   TORCH_CHECK(q.stride(-1) == 1, "q rows must be contiguous");
   const int B = q.size(0);
@@ -487,6 +535,20 @@ at::Tensor paged_decode(const at::Tensor& q, const at::Tensor& k_cache, const at
   auto out = at::empty({B, Hq * D}, q.options());
   auto tmp_out = at::empty({B, Hq, max_parts, D}, q.options().dtype(at::kFloat));
   auto tmp_ml = at::empty({B, Hq, max_parts, 2}, q.options().dtype(at::kFloat));
+  if (f8) {   // FP8 cache: the per-row register kernel over 1-byte elements (G = 4 or 8)
+    // `order` is dropped here: it only permutes the workgroup dispatch of the bf16 ring / MFMA
+    // kernels (results do not depend on it) and the register kernel takes rows in grid order
+    TORCH_CHECK(Hq == 4 * Hkv || Hq == 8 * Hkv, "paged_decode (fp8 cache): 4 or 8 query heads per KV head");
+    TORCH_CHECK(q.dim() == 2 && q.size(1) >= Hq * D && q.stride(0) % 8 == 0, "paged_decode (fp8 cache): q rows");
+    CHECK_ALIGN16(q);
+    TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) >= B && context_lens.numel() >= B,
+                "paged_decode (fp8 cache): B rows");
+    CHECK_RC(docqa_paged_decode8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                 block_tables.data_ptr<int>(), block_tables.size(1), context_lens.data_ptr<int>(),
+                                 out.data_ptr(), Hq * D, tmp_out.data_ptr<float>(), tmp_ml.data_ptr<float>(), B, Hq,
+                                 Hkv, D, BS, max_parts, (float)scale, stream()), "paged_decode (fp8 cache)");
+    return out;
+  }
   CHECK_RC(docqa_paged_decode(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
                               block_tables.data_ptr<int>(), block_tables.size(1),
                               context_lens.data_ptr<int>(), out.data_ptr(), Hq * D,
@@ -617,7 +679,12 @@ at::Tensor paged_decode_cascade_split(const at::Tensor& q, at::Tensor k_cache, a
                                       int64_t Hq, double scale, const at::Tensor& prefix_table,
                                       const at::Tensor& prefix_len, int64_t nchunk, const at::Tensor& plan,
                                       bool defer, const c10::optional<at::Tensor>& tick, bool inline_prefix) {
-  CHECK_GPU(q); CHECK_BF16(q); CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+  CHECK_GPU(q); CHECK_BF16(q);
+  TORCH_CHECK(k_cache.dim() == 4, "k_cache: [num_blocks, Hkv, BS, D]");
+  const bool f8 = kv_fp8(k_cache, v_cache, k_cache.size(1), k_cache.size(3));
+  // FP8 cache: only the wave-parallel kernel over a split plan built from block 0 reads it
+  TORCH_CHECK(!f8 || (inline_prefix && !defer && plan.dim() == 3 && plan.size(0) == 2),
+              "split decode (fp8 cache): a [2, cap, 8] plan from block 0 (inline_prefix), not deferred");
   CHECK_I32(block_tables); CHECK_I32(context_lens); CHECK_CONTIG(block_tables);
   CHECK_I32(prefix_table); CHECK_I32(prefix_len); CHECK_CONTIG(prefix_table);
   CHECK_I32(plan); CHECK_CONTIG(plan);
@@ -635,8 +702,9 @@ at::Tensor paged_decode_cascade_split(const at::Tensor& q, at::Tensor k_cache, a
   c10::DeviceGuard g(q.device());
   auto out = at::empty({B, Hq * D}, q.options());
   auto f32 = q.options().dtype(at::kFloat);
-  auto pacc = at::empty({nchunk, B, Hq, D}, f32);
-  auto pml = at::empty({nchunk, B, Hq, 2}, f32);
+  // prefix-kernel partials: not needed by the FP8 path (no prefix kernel, returns below)
+  auto pacc = f8 ? at::Tensor() : at::empty({nchunk, B, Hq, D}, f32);
+  auto pml = f8 ? at::Tensor() : at::empty({nchunk, B, Hq, 2}, f32);
   auto ws_acc = at::empty({cap, Hkv, 16, D}, f32);
   auto ws_ml = at::empty({cap, Hkv, 16, 2}, f32);
   const int* pp = plan.data_ptr<int>();
@@ -645,6 +713,17 @@ at::Tensor paged_decode_cascade_split(const at::Tensor& q, at::Tensor k_cache, a
     CHECK_GPU((*tick)); CHECK_I32((*tick));
     TORCH_CHECK(tick->numel() >= (int64_t)cap * Hkv, "split decode: tick needs cap * Hkv entries");
     tick_ptr = tick->data_ptr<int>();
+  }
+  if (f8) {
+    TORCH_CHECK(q.dim() == 2 && q.size(1) >= Hq * D && q.stride(0) % 8 == 0, "split decode (fp8 cache): q rows");
+    CHECK_ALIGN16(q);
+    CHECK_RC(docqa_paged_decode_group_wave8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                            block_tables.data_ptr<int>(), block_tables.size(1),
+                                            context_lens.data_ptr<int>(), out.data_ptr(), Hq * D, B, Hq, Hkv, BS,
+                                            (float)scale, pp, pp + 8 * cap, cap, ws_acc.data_ptr<float>(),
+                                            ws_ml.data_ptr<float>(), stream(), tick_ptr),
+             "paged_decode_cascade_split (fp8 cache)");
+    return out;
   }
   if (plan.size(0) == 3) {
     CHECK_RC(docqa_paged_decode_cascade_persist(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
@@ -766,7 +845,8 @@ at::Tensor flash_prefill_paged(const at::Tensor& qkv, const at::Tensor& cu_seqle
                                int64_t Hq, int64_t Hkv, int64_t D, double scale,
                                const at::Tensor& k_cache, const at::Tensor& v_cache,
                                const at::Tensor& block_tables, const at::Tensor& ctx_start) {
-  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_I32(cu_seqlens); CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_I32(cu_seqlens);
+  const bool f8 = kv_fp8(k_cache, v_cache, Hkv, D);
   CHECK_I32(block_tables); CHECK_I32(ctx_start); CHECK_CONTIG(block_tables);
   TORCH_CHECK(qkv.stride(-1) == 1 && qkv.size(-1) == (Hq + 2 * Hkv) * D, "qkv layout mismatch");
   TORCH_CHECK(k_cache.size(1) == Hkv && k_cache.size(3) == D, "cache layout mismatch");
@@ -775,6 +855,14 @@ at::Tensor flash_prefill_paged(const at::Tensor& qkv, const at::Tensor& cu_seqle
   TORCH_CHECK(block_tables.size(0) == B && ctx_start.numel() == B, "per-sequence metadata mismatch");
   c10::DeviceGuard g(qkv.device());
   auto out = at::empty({T, Hq * D}, qkv.options());
+  if (f8) {   // FP8 cache: the paged gather widens the codes, everything after it is the bf16 kernel
+    CHECK_RC(docqa_flash_prefill_paged8(qkv.data_ptr(), qkv.size(-1), cu_seqlens.data_ptr<int>(),
+                                        out.data_ptr(), Hq * D, B, max_len, Hq, Hkv, D, (float)scale,
+                                        k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr<int>(),
+                                        block_tables.size(1), ctx_start.data_ptr<int>(), k_cache.size(2),
+                                        stream()), "flash_prefill_paged (fp8 cache)");
+    return out;
+  }
   CHECK_RC(docqa_flash_prefill_paged(qkv.data_ptr(), qkv.size(-1), cu_seqlens.data_ptr<int>(),
                                      out.data_ptr(), Hq * D, B, max_len, Hq, Hkv, D, (float)scale,
                                      k_cache.data_ptr(), v_cache.data_ptr(), block_tables.data_ptr<int>(),
@@ -1606,6 +1694,7 @@ TORCH_LIBRARY(docqa, m) {
         "Tensor context_lens, int Hq, float scale, Tensor prefix_table, Tensor prefix_len, int nchunk, "
         "Tensor groups) -> Tensor");
   m.def("kv_copy_rows(Tensor caches, Tensor tab, int num_blocks, int Hkv, int BS, int D) -> ()");
+  m.def("kv_copy_rows8(Tensor caches, Tensor tab, int num_blocks, int Hkv, int BS, int D) -> ()");
   m.def("paged_decode_cascade_split(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
         "Tensor context_lens, int Hq, float scale, Tensor prefix_table, Tensor prefix_len, int nchunk, "
         "Tensor plan, bool defer=False, Tensor(t!)? tick=None, bool inline_prefix=False) -> Tensor");
@@ -1694,6 +1783,7 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("paged_decode_cascade_split", &paged_decode_cascade_split);
   m.impl("paged_decode_grouped_fused", &paged_decode_grouped_fused);
   m.impl("kv_copy_rows", &kv_copy_rows);
+  m.impl("kv_copy_rows8", &kv_copy_rows8);
   m.impl("ar_run", &ar_run);
   m.impl("add_rmsnorm_splitk", &add_rmsnorm_splitk);
   m.impl("rope_cache_splitk", &rope_cache_splitk);

@@ -46,6 +46,17 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return v;
 }
 
+// 8 OCP e4m3 codes -> their bf16 values, packed like 8 bf16 in a uint4
+// (v_cvt_scalef32_pk_bf16_fp8 at scale 1.0: exact, every e4m3 value is a bf16 value)
+__device__ __forceinline__ uint4 widen8_fp8(uint2 c) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.x, 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.x, 1.0f, true);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.y, 1.0f, false);
+  const bf16x2 e = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c.y, 1.0f, true);
+  return uint4{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, d),
+               __builtin_bit_cast(uint32_t, e)};
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

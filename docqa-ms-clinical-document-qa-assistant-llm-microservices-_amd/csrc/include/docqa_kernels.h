@@ -19,6 +19,32 @@ int docqa_rope_cache(void* qkv, const int* positions, const float* cos_sin,
                      const int* slot_mapping, void* k_cache, void* v_cache, int T, int Hq,
                      int Hkv, int D, int row_stride, int BS, hipStream_t s);
 
+// FP8 (OCP e4m3, no scales) paged KV cache: the *8 entry points take caches of 1-byte codes
+// in the same [num_blocks, Hkv, BS, D] layout (csrc/kernels/rope_cache.hip, attn_prefill.hip,
+// attn_decode.hip)
+int docqa_kv_copy_rows8(const uint64_t* caches, int ntensors, const int* tab, int n, int nblocks, int Hkv, int BS,
+                        int D, hipStream_t s);
+int docqa_rope_cache8(void* qkv, const int* positions, const float* cos_sin, const int* slot_mapping,
+                      void* k_cache, void* v_cache, int T, int Hq, int Hkv, int D, int row_stride, int BS,
+                      hipStream_t s);
+int docqa_rope_cache_splitk8(const void* P, int slab16, int S, void* qkv_out, const int* positions,
+                             const float* cos_sin, const int* slot_mapping, void* k_cache, void* v_cache, int T,
+                             int Hq, int Hkv, int D, int row_stride, int BS, hipStream_t s);
+int docqa_flash_prefill_paged8(const void* qkv, int row_stride, const int* cu_seqlens, void* out,
+                               int o_stride, int B, int max_len, int Hq, int Hkv, int head_dim,
+                               float scale, const void* k_cache, const void* v_cache,
+                               const int* block_tables, int maxb, const int* ctx_start, int BS,
+                               hipStream_t s);
+int docqa_paged_decode8(const void* q, int q_stride, const void* k_cache, const void* v_cache,
+                        const int* block_tables, int maxb, const int* context_lens, void* out,
+                        int out_stride, float* tmp_out, float* tmp_ml, int B, int Hq, int Hkv,
+                        int D, int BS, int max_parts, float scale, hipStream_t s);
+int docqa_paged_decode_group_wave8(const void* q, int q_stride, const void* k_cache, const void* v_cache,
+                                   const int* block_tables, int maxb, const int* context_lens, void* out,
+                                   int out_stride, int B, int Hq, int Hkv, int BS, float scale, const int* items,
+                                   const int* merges, int cap, float* ws_acc, float* ws_ml, hipStream_t s,
+                                   int* tick);
+
 int docqa_silu_mul(const void* gu, void* out, int T, int I, int interleaved, hipStream_t s);
 int docqa_silu_mul_splitk16(const void* P, void* out, int S, int T, int I, hipStream_t s);
 int docqa_silu_mul_splitk(const float* P, void* out, int S, int T, int I, hipStream_t s);

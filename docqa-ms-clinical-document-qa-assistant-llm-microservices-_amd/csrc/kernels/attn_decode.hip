@@ -31,6 +31,7 @@
 #include "docqa_norm_row.h"
 #include <float.h>
 #include <stdlib.h>
+#include <type_traits>
 
 using namespace docqa;
 
@@ -412,7 +413,12 @@ __device__ __forceinline__ bool last_arriver_merge(const float* __restrict__ tmp
 // DIRECT (one partition per sequence, the batch-64 serving case): the workgroup already
 // holds the whole softmax, so it writes the normalised bf16 output itself and the
 // partition-merge launch is skipped (one kernel boundary less per layer).
-template <int G, int D, int U, bool DIRECT, int OCC = 2>
+// F8: the caches hold OCP e4m3 codes (FP8 paged KV, no scales), one byte per element in the
+// same layout.  A 16-lane group still owns one token row -- now 16 lanes x 8 B = one 128-B
+// row, a wave reads 4 consecutive tokens = 512 B contiguous per instruction -- and the codes
+// are widened to their exact bf16 image in registers in front of the same dot / online-softmax
+// / P.V code, so the arithmetic is the bf16 kernel's on the image.
+template <int G, int D, int U, bool DIRECT, int OCC = 2, bool F8 = false>
 __global__ __launch_bounds__(256, OCC) void paged_decode_kernel(
     const uint16_t* __restrict__ q, int q_stride, const uint16_t* __restrict__ k_cache,
     const uint16_t* __restrict__ v_cache, const int* __restrict__ block_tables, int maxb,
@@ -471,7 +477,8 @@ __global__ __launch_bounds__(256, OCC) void paged_decode_kernel(
   // Loads are unconditional (tail tokens re-read the slice's last valid row and are
   // masked in compute): a per-element "load or skip" branch makes hipcc wait vmcnt(0)
   // around every load and serialises the stream (guide §5 trap (c)).
-  auto load = [&](uint4 (&kr)[U], uint4 (&vr)[U], bool (&ok)[U], int base) {
+  using Row = typename std::conditional<F8, uint2, uint4>::type;   // 8 elements of a K / V row
+  auto load = [&](Row (&kr)[U], Row (&vr)[U], bool (&ok)[U], int base) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int tok = base + 16 * u;
@@ -479,15 +486,30 @@ __global__ __launch_bounds__(256, OCC) void paged_decode_kernel(
       const int t = start + min(tok, n - 1);
       const size_t off = (size_t)bt[t >> log2BS] * blk_stride + head_off +
                          (size_t)(t & (BS - 1)) * D;
-      kr[u] = *reinterpret_cast<const uint4*>(k_cache + off);
-      vr[u] = *reinterpret_cast<const uint4*>(v_cache + off);
+      if constexpr (F8) {   // element offset == byte offset
+        kr[u] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(k_cache) + off);
+        vr[u] = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(v_cache) + off);
+      } else {
+        kr[u] = *reinterpret_cast<const uint4*>(k_cache + off);
+        vr[u] = *reinterpret_cast<const uint4*>(v_cache + off);
+      }
     }
   };
-  auto compute = [&](const uint4 (&kr)[U], const uint4 (&vr)[U], const bool (&ok)[U]) {
-    attend_rows<G, U>(kr, vr, ok, qv, qs, m, l, acc);
+  auto compute = [&](const Row (&kr)[U], const Row (&vr)[U], const bool (&ok)[U]) {
+    if constexpr (F8) {
+      uint4 kw[U], vw[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        kw[u] = widen8_fp8(kr[u]);
+        vw[u] = widen8_fp8(vr[u]);
+      }
+      attend_rows<G, U>(kw, vw, ok, qv, qs, m, l, acc);
+    } else {
+      attend_rows<G, U>(kr, vr, ok, qv, qs, m, l, acc);
+    }
   };
 
-  uint4 kA[U], vA[U], kB[U], vB[U];
+  Row kA[U], vA[U], kB[U], vB[U];
   bool okA[U], okB[U];
   int base = wave * 4 + tg;
   if (base < n) load(kA, vA, okA, base);
@@ -1666,6 +1688,269 @@ __global__ __launch_bounds__(64 * WAVES) void paged_decode_group_wave_kernel(
                           context_lens, B, Hkv, out, out_stride, kvh, P);
 }
 
+// The wave-parallel grouped decode over an FP8 (e4m3, no scales) paged cache: the work items,
+// tile list, Q fragments, online softmax, wave combine and epilogue (group_item_finish: split
+// partials, ticket merge, merge kernel) of paged_decode_group_wave_kernel<4, .>; only the K/V
+// stream and the two LDS -> MFMA operand reads differ.  Q, P and every MFMA stay bf16: codes
+// are widened in registers with v_cvt_scalef32_pk_bf16_fp8 at scale 1.0 (exact).
+//   * A quarter tile is 16 tokens x 128 B = 2 KB of K + 2 KB of V: TWO 1-KB LDS-DMA
+//     wave-instructions each (piece c = tile rows 8c .. 8c+7, lane = (row lane >> 3, 16-B
+//     slot lane & 7)), so a staged tile is 4 vmcnt units (8 in the bf16 kernel) and the
+//     counted wait is vmcnt(4 (NSRW - 1)).
+//   * The freed LDS goes to RING DEPTH, not to workgroups per CU: NSRW = 4 slots of 4 KB per
+//     wave = 64 KB per workgroup, the bf16 kernel's footprint (two workgroups per CU), with
+//     three tiles (12 KB) in flight per wave behind the one being consumed where the bf16
+//     kernel has one (8 KB).  The wave combine needs 32.5 KB of the ring, so NSRW >= 3 anyway.
+//   * K operand (A of mfma_16x16x32_bf16: lane (token hl, k-group lg) holds dims 32 ks + 8 lg
+//     .. + 7): one ds_read_b64 + widen.  LDS row = token, 16-B slot = chunk ^ ((row >> 1) & 7),
+//     placed by the DMA source address.  ds_read_b64 is served in two 32-lane groups with bank
+//     = (addr / 4) % 64, i.e. 32 8-B slots per 256-B bank row; a group is lg in {0, 1} or
+//     {2, 3}, all 16 hl: chunk = 2 ks + (lg >> 1) is one value, so the slot of a lane is
+//     16 (hl & 1) + 2 ((chunk ^ (hl >> 1)) & 7) + (lg & 1) -- hl >> 1 runs over 0..7, the XOR
+//     makes the 8 chunks distinct, and (hl & 1, lg & 1) pick the rest: 32 distinct slots.
+//   * V operand (A of mfma_16x16x16bf16_1k: lane (dim row hl, k-group lg) needs ONE dim of
+//     tokens 4 lg .. 4 lg + 3, which are 128 B apart -- ds_read_tr16_b64 no longer applies).
+//     Chosen: a 4 x 4 byte transpose in registers with a permuted dim -> MFMA map.  The lane
+//     reads 8 B = dims 8 hl .. 8 hl + 7 of each of its four tokens (4 ds_read_b64 per tile,
+//     where the bf16 kernel issues 8 transposed reads), transposes the two 4 x 4 byte blocks
+//     with 16 v_perm_b32, and widens each transposed word (one dim, four tokens) into the A
+//     operand of MFMA idx = 0..7, whose row hl is dim 8 hl + idx.  So o8[idx][r] of lane
+//     (hl, lg) is dim 32 lg + 8 r + idx of column hl, and the wave combine stores
+//     {o8[4 ih + 0..3][r]} as one 16-B vector where the epilogue's layout (dim 16 dt + 4 lg'
+//     + r', lane 16 lg' + hl) wants it: dt = 2 lg + (r >> 1), lg' = 2 (r & 1) + ih.
+//     Bank pattern: token t sits in LDS row t ^ ((t >> 2) & 1) (DMA source address again), no
+//     chunk swizzle.  In a 32-lane group lg = 2 a + {0, 1} reads tokens 8 a + j and 8 a + 4 + j:
+//     rows 8 a + j and (8 a + 4 + j) ^ 1 have opposite parity = opposite 128-B halves of the
+//     bank row, and the 16 hl of one lg cover their row's 128 B exactly: 32 distinct 8-B slots.
+__device__ __forceinline__ i16x4 widen4_fp8(uint32_t c) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, true);
+  const uint2 u{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b)};
+  return __builtin_bit_cast(i16x4, u);
+}
+
+template <int NSRW>
+__global__ __launch_bounds__(256) void paged_decode_group_wave8_kernel(
+    const uint16_t* __restrict__ q, int q_stride, const uint8_t* __restrict__ k_cache,
+    const uint8_t* __restrict__ v_cache, const int* __restrict__ block_tables, int maxb,
+    const int* __restrict__ context_lens, int B, int Hkv, float scale,
+    uint16_t* __restrict__ out, int out_stride, const int* __restrict__ groups, CascadeIn ci,
+    float* __restrict__ ws_acc, float* __restrict__ ws_ml, const int* __restrict__ merges, int* __restrict__ tick) {
+  constexpr int WAVES = 4, G = 4, R = 4, D = 128, TQ = 16, MAXT = kGroupMaxPos * 16;
+  constexpr int TILE = TQ * D;                   // bytes of one K (or V) quarter tile: 2 KB
+  constexpr int WSLOT = 2 * TILE;                // K + V of one ring slot
+  constexpr int NDT = 8 / WAVES;
+  static_assert(WAVES * NSRW * WSLOT >= WAVES * 8 * 64 * 16 + WAVES * 16 * 2 * 4, "ring reused by the merge");
+  __shared__ __attribute__((aligned(16))) uint8_t ring[WAVES * NSRW * WSLOT];
+  __shared__ unsigned s_tl[MAXT];                // block id << 12 | pos << 6 | quarter << 4 | row mask
+  __shared__ int s_nt;
+
+  const int kvh = blockIdx.x, grp = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hl = lane & 15, lg = lane >> 4;
+  const int P = ci.plen ? *ci.plen : 0;
+  const int* gp = groups + 8 * grp;
+  int rows[R], Ls[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int row = gp[r];
+    rows[r] = row >= 0 && row < B ? row : -1;
+    Ls[r] = rows[r] >= 0 ? context_lens[rows[r]] : 0;
+  }
+  if (rows[0] < 0 && rows[1] < 0 && rows[2] < 0 && rows[3] < 0) return;   // unused item
+  const int lo = gp[4], hi = min(gp[5], maxb), part = gp[6];
+
+  // ---- tile list: as paged_decode_group_wave_kernel
+  if (wave == 0) {
+    const int pos = max(P >> 6, lo) + lane;
+    int ids[R], nq[R], mk[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) ids[r] = rows[r] >= 0 && pos < hi ? block_tables[(size_t)rows[r] * maxb + pos] : -1;
+    bool alive[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      alive[r] = pos < hi && 64 * pos < Ls[r];
+      ids[r] = alive[r] ? ids[r] : -1;
+    }
+    int cnt = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      bool first = alive[r];
+#pragma unroll
+      for (int r2 = 0; r2 < r; ++r2) first = first && !(alive[r2] && ids[r2] == ids[r]);
+      int mask = 0, need = 0;
+      if (first) {
+#pragma unroll
+        for (int r2 = 0; r2 < R; ++r2)
+          if (alive[r2] && ids[r2] == ids[r]) {
+            mask |= 1 << r2;
+            need = max(need, min(4, (Ls[r2] - 64 * pos + TQ - 1) / TQ));
+          }
+      }
+      nq[r] = need;
+      mk[r] = mask;
+      cnt += need;
+    }
+    int off = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(off, o, 64);
+      if (lane >= o) off += v;
+    }
+    const int total = __shfl(off, 63, 64);
+    off -= cnt;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      for (int h = 0; h < nq[r]; ++h) s_tl[off++] = ((unsigned)ids[r] << 12) | (pos << 6) | (h << 4) | mk[r];
+    if (lane == 0) s_nt = total;
+  }
+  const int crow = rows[hl >> 2], cL = Ls[hl >> 2], cbit = 1 << (hl >> 2);
+  bf16x8 qf[4];
+  {
+    const uint16_t* qp = q + (size_t)max(crow, 0) * q_stride + (size_t)(kvh * G + (hl & 3)) * D + lg * 8;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const uint4 v = crow >= 0 ? *reinterpret_cast<const uint4*>(qp + ks * 32) : make_uint4(0, 0, 0, 0);
+      qf[ks] = __builtin_bit_cast(bf16x8, v);
+    }
+  }
+  __syncthreads();                               // tile list + Q landed (fence drains vmcnt)
+  const int nt = s_nt;
+
+  const float qs = scale * kLog2e;
+  const uint32_t wbase = lds_u32(ring) + (uint32_t)(wave * NSRW * WSLOT);
+  const int prow = lane >> 3, pslot = lane & 7;
+  const int mine_nt = nt > wave ? (nt - wave + WAVES - 1) / WAVES : 0;   // this wave's tiles: wave + WAVES i
+  auto stage = [&](int i) {
+    const unsigned e = s_tl[wave + WAVES * i];
+    const size_t row0 = ((size_t)(e >> 12) * Hkv + kvh) * 64 + ((e >> 4) & 3) * TQ;
+    const uint8_t* kp = k_cache + row0 * D;
+    const uint8_t* vp = v_cache + row0 * D;
+    const uint32_t dst = wbase + (uint32_t)((i % NSRW) * WSLOT);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {                // 1 KB piece = LDS rows 8c .. 8c+7 of the tile
+      const int t = 8 * c + prow;
+      glds16<true>(kp + t * D + ((pslot ^ ((t >> 1) & 7)) << 4), dst + c * 1024);
+      glds16<true>(vp + (t ^ ((t >> 2) & 1)) * D + (pslot << 4), dst + TILE + c * 1024);
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < NSRW - 1; ++i)
+    if (i < mine_nt) stage(i);
+  float m = -FLT_MAX, l = 0.f;
+  f32x4 o8[8];
+#pragma unroll
+  for (int dt = 0; dt < 8; ++dt) o8[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < mine_nt; ++i) {
+    if (i + NSRW - 1 < mine_nt) {
+      stage(i + NSRW - 1);
+      wait_vmcnt<4 * (NSRW - 1)>();              // tile i landed; the next NSRW - 1 may fly
+    } else {
+      wait_vmcnt<0>();
+    }
+    const unsigned e = s_tl[wave + WAVES * i];
+    const bool mine = (e & cbit) != 0;
+    const int base = ((e >> 6) & 63) * 64 + ((e >> 4) & 3) * TQ;
+    const uint8_t* kt = ring + (wave * NSRW + i % NSRW) * WSLOT;
+    const uint8_t* vt = kt + TILE;
+    f32x4 x = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const uint2 c = *reinterpret_cast<const uint2*>(kt + hl * D + (((2 * ks + (lg >> 1)) ^ ((hl >> 1) & 7)) << 4) +
+                                                      (lg & 1) * 8);
+      const bf16x8 a = __builtin_bit_cast(bf16x8, widen8_fp8(c));
+      x = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, qf[ks], x, 0, 0, 0);
+    }
+    // ---- per-column online softmax: lane = tokens 4 lg + r of column hl
+    float mx = -FLT_MAX;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int tok = base + 4 * lg + r;
+      const float v = (mine && tok < cL) ? x[r] * qs : -FLT_MAX;
+      x[r] = v;
+      mx = fmaxf(mx, v);
+    }
+    mx = rows4_max(mx);
+    const float m_new = fmaxf(m, mx);
+    const float alpha = m_new == -FLT_MAX ? 1.f : __builtin_amdgcn_exp2f(m - m_new);
+    float ps = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float p = x[r] == -FLT_MAX ? 0.f : __builtin_amdgcn_exp2f(x[r] - m_new);
+      x[r] = p;
+      ps += p;
+    }
+    ps = rows4_sum(ps);
+    l = l * alpha + ps;
+    m = m_new;
+    // ---- O^T += V^T P^T over all 128 dims: MFMA idx covers dims 8 hl' + idx (hl' = its row)
+    i16x4 pb;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pb[r] = (short)f2bf(x[r]);
+    uint2 w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = 4 * lg + j;
+      w[j] = *reinterpret_cast<const uint2*>(vt + (t ^ ((t >> 2) & 1)) * D + hl * 8);
+    }
+#pragma unroll
+    for (int ih = 0; ih < 2; ++ih) {
+      const uint32_t w0 = ih ? w[0].y : w[0].x, w1 = ih ? w[1].y : w[1].x;
+      const uint32_t w2 = ih ? w[2].y : w[2].x, w3 = ih ? w[3].y : w[3].x;
+      // 4 x 4 byte transpose: w_j = 4 dims of token j  ->  tr[i] = 4 tokens of dim i
+      // (v_perm_b32 selectors 0..3: bytes of the second operand, 4..7: of the first)
+      const uint32_t a01 = __builtin_amdgcn_perm(w1, w0, 0x05010400u), a23 = __builtin_amdgcn_perm(w3, w2, 0x05010400u);
+      const uint32_t c01 = __builtin_amdgcn_perm(w1, w0, 0x07030602u), c23 = __builtin_amdgcn_perm(w3, w2, 0x07030602u);
+      const uint32_t tr[4] = {__builtin_amdgcn_perm(a23, a01, 0x05040100u), __builtin_amdgcn_perm(a23, a01, 0x07060302u),
+                              __builtin_amdgcn_perm(c23, c01, 0x05040100u), __builtin_amdgcn_perm(c23, c01, 0x07060302u)};
+#pragma unroll
+      for (int i4 = 0; i4 < 4; ++i4) {
+        const int idx = 4 * ih + i4;
+        o8[idx] *= alpha;
+        o8[idx] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(widen4_fp8(tr[i4]), pb, o8[idx], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- combine the waves' states through LDS (the ring is free once every wave is done), in
+  // the bf16 kernel's layout: s_o[(wave 8 + dt) 64 + 16 lg' + hl][r'] = dim 16 dt + 4 lg' + r'
+  __syncthreads();
+  f32x4* s_o = reinterpret_cast<f32x4*>(ring);                       // [wave][dt][lane]
+  float* s_ml = reinterpret_cast<float*>(ring) + WAVES * 8 * 64 * 4; // [wave][column][2]
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int ih = 0; ih < 2; ++ih)
+      s_o[(wave * 8 + 2 * lg + (r >> 1)) * 64 + (2 * (r & 1) + ih) * 16 + hl] =
+          f32x4{o8[4 * ih][r], o8[4 * ih + 1][r], o8[4 * ih + 2][r], o8[4 * ih + 3][r]};
+  if (lg == 0) {
+    s_ml[(wave * 16 + hl) * 2] = m;
+    s_ml[(wave * 16 + hl) * 2 + 1] = l;
+  }
+  __syncthreads();
+  float mw[WAVES], lw[WAVES], M = -FLT_MAX;
+#pragma unroll
+  for (int u = 0; u < WAVES; ++u) {
+    mw[u] = s_ml[(u * 16 + hl) * 2];
+    lw[u] = s_ml[(u * 16 + hl) * 2 + 1];
+    M = fmaxf(M, mw[u]);
+  }
+  f32x4 acc[NDT];
+#pragma unroll
+  for (int dd = 0; dd < NDT; ++dd) acc[dd] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float L = 0.f;
+#pragma unroll
+  for (int u = 0; u < WAVES; ++u) {
+    const float f = mw[u] == -FLT_MAX ? 0.f : exp2f(mw[u] - M);
+    L += f * lw[u];
+#pragma unroll
+    for (int dd = 0; dd < NDT; ++dd) acc[dd] += f * s_o[(u * 8 + NDT * wave + dd) * 64 + lane];
+  }
+  group_item_finish<true, NDT>(M, L, acc, part, crow, cL, hl, lg, wave, tid, gp, merges, tick, ws_acc, ws_ml, ci,
+                               context_lens, B, Hkv, out, out_stride, kvh, P);
+}
+
 // Combines the partials of every split group (merges [cap, 8] = (4 row ids, first slot,
 // slots, 0, 0); slots 0: nothing to merge) with the cascade prefix partials of each column's
 // row, then normalises: thread = (column, 8 dims).
@@ -2244,6 +2529,28 @@ int docqa_paged_decode_cascade_split(const void* q, int q_stride, void* k_cache,
   return 0;
 }
 
+// Grouped split decode over an FP8 (e4m3) cache: the wave-parallel kernel only, with a split
+// plan built from block 0 (every group attends its whole context -- no prefix kernel, no
+// cascade partials), split groups merged by ticket (tick) or by the merge kernel.
+int docqa_paged_decode_group_wave8(const void* q, int q_stride, const void* k_cache, const void* v_cache,
+                                   const int* block_tables, int maxb, const int* context_lens, void* out,
+                                   int out_stride, int B, int Hq, int Hkv, int BS, float scale, const int* items,
+                                   const int* merges, int cap, float* ws_acc, float* ws_ml, hipStream_t s,
+                                   int* tick) {
+  if (B == 0) return 0;
+  if (BS != 64 || maxb > kGroupMaxTable || Hq != 4 * Hkv || cap < 1) return -1;
+  const CascadeIn ci{nullptr, nullptr, nullptr, 1, nullptr};
+  paged_decode_group_wave8_kernel<4><<<dim3(Hkv, cap), 256, 0, s>>>(
+      (const uint16_t*)q, q_stride, (const uint8_t*)k_cache, (const uint8_t*)v_cache, block_tables, maxb,
+      context_lens, B, Hkv, scale, (uint16_t*)out, out_stride, items, ci, ws_acc, ws_ml, merges, tick);
+  DOCQA_CHECK_LAUNCH();
+  if (tick) return 0;
+  group_split_merge_kernel<<<dim3(Hkv, (cap + 1) / 2), 256, 0, s>>>(merges, ws_acc, ws_ml, context_lens, B, Hkv,
+                                                                   (uint16_t*)out, out_stride, ci);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
 // Persistent grouped cascade decode: plan [3, cap, 8] = items (4 rows, first position, end
 // position, slot, 0), merges (4 rows, first slot, slots, 0, 0) covering EVERY group, bins
 // (<= 8 item indices, -1 = none) -- group_persist_bins(cap, Hkv) of them.
@@ -2442,6 +2749,35 @@ int docqa_paged_decode(const void* q, int q_stride, const void* k_cache, const v
     paged_decode_reduce<128><<<dim3(Hq, B), 128, 0, s>>>(tmp_out, tmp_ml, context_lens,
                                                          (uint16_t*)out, out_stride, Hq,
                                                          max_parts);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// Per-row decode attention over an FP8 (e4m3) cache: same grid, partitions and merge as
+// docqa_paged_decode; G = 4 (U = 4 rows in flight per buffer) and G = 8 (U = 2).
+int docqa_paged_decode8(const void* q, int q_stride, const void* k_cache, const void* v_cache,
+                        const int* block_tables, int maxb, const int* context_lens, void* out,
+                        int out_stride, float* tmp_out, float* tmp_ml, int B, int Hq, int Hkv,
+                        int D, int BS, int max_parts, float scale, hipStream_t s) {
+  if (B == 0) return 0;
+  if (D != 128 || BS != 64 || Hkv <= 0 || (Hq != 4 * Hkv && Hq != 8 * Hkv) || max_parts < 1) return -1;
+  const dim3 grid(Hkv, B, max_parts);   // partitions slowest: see kDecodeGridNote
+  const bool direct = max_parts == 1;
+#define DEC8(GG, UU, DIR)                                                                          \
+  paged_decode_kernel<GG, 128, UU, DIR, 2, true><<<grid, 256, 0, s>>>(                             \
+      (const uint16_t*)q, q_stride, (const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables, \
+      maxb, context_lens, tmp_out, tmp_ml, Hkv, BS, 6, max_parts, scale, (uint16_t*)out, out_stride)
+  if (Hq == 4 * Hkv) {
+    if (direct) DEC8(4, 4, true);
+    else DEC8(4, 4, false);
+  } else {
+    if (direct) DEC8(8, 2, true);
+    else DEC8(8, 2, false);
+  }
+#undef DEC8
+  if (!direct)
+    paged_decode_reduce<128><<<dim3(Hq, B), 128, 0, s>>>(tmp_out, tmp_ml, context_lens, (uint16_t*)out,
+                                                         out_stride, Hq, max_parts);
   DOCQA_CHECK_LAUNCH();
   return 0;
 }

@@ -64,6 +64,7 @@ struct PagedKV {
   const int* ctx_start;
   int BS;
   int log2BS;
+  int f8 = 0;   // k / v hold OCP e4m3 codes (1 byte per element, same [NB, Hkv, BS, D] shape)
 };
 
 // PFX (cascade decode, docqa_cascade.h): the query rows are the B sequences of a decode
@@ -74,11 +75,15 @@ struct PagedKV {
 // G = 4, WPH = 1 (32-row tiles, 4 waves): at most 256 VGPRs so that two workgroups share a
 // CU and one's prologue (Q, block ids, first K/V tile: three dependent round trips) runs
 // under the other's main loop -- unbounded, hipcc spends ~300 and keeps one per CU
-template <int D, bool CAUSAL, bool PAGED, int G, int WPH, bool PFX = false>
+template <int D, bool CAUSAL, bool PAGED, int G, int WPH, bool PFX = false, bool F8 = false>
 __global__ __launch_bounds__(64 * G * WPH, (G == 4 && WPH == 1) ? 2 : 1) void flash_prefill_kernel(
     const uint16_t* __restrict__ qkv, int row_stride, const int* __restrict__ cu_seqlens,
     uint16_t* __restrict__ out, int o_stride, int Hq, int Hkv, float scale, PagedKV pk,
     CascadeOut co) {
+  // F8 (FP8 paged KV): the per-row block-table form only.  The shared-prefix-table form (PFX)
+  // is the cascade's prefix kernel, which is never routed to an FP8 cache (ops.cascade_ok), so
+  // it is not built rather than left untested.
+  static_assert(!F8 || (PAGED && !PFX), "FP8 KV: paged prefill with per-row block tables only");
   constexpr int NT = 64 * G * WPH;              // threads
   constexpr int QBW = 32 * WPH;                 // query rows per workgroup
   __shared__ __attribute__((aligned(16))) uint16_t smem[2 * KB * D];
@@ -196,8 +201,15 @@ __global__ __launch_bounds__(64 * G * WPH, (G == 4 && WPH == 1) ? 2 : 1) void fl
           const int blk = bt_lds ? s_bt[key >> pk.log2BS]
                                  : pk.block_tables[(size_t)(PFX ? 0 : b) * pk.maxb + (key >> pk.log2BS)];
           const size_t off = (((size_t)blk * Hkv + kvh) * pk.BS + (key & (pk.BS - 1))) * D + ch * 8;
-          rk[i] = *reinterpret_cast<const uint4*>(pk.k + off);
-          rv[i] = *reinterpret_cast<const uint4*>(pk.v + off);
+          if constexpr (F8) {
+            // FP8 cache: 8 e4m3 codes (8 B) per lane, widened to their exact bf16 image in
+            // registers -- the LDS tiles, swizzles and MFMAs are the bf16 path's
+            rk[i] = widen8_fp8(*reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(pk.k) + off));
+            rv[i] = widen8_fp8(*reinterpret_cast<const uint2*>(reinterpret_cast<const uint8_t*>(pk.v) + off));
+          } else {
+            rk[i] = *reinterpret_cast<const uint4*>(pk.k + off);
+            rv[i] = *reinterpret_cast<const uint4*>(pk.v + off);
+          }
         } else {
           rk[i] = *reinterpret_cast<const uint4*>(kbase + (size_t)key * row_stride + ch * 8);
           rv[i] = *reinterpret_cast<const uint4*>(vbase + (size_t)key * row_stride + ch * 8);
@@ -368,7 +380,10 @@ static void launch_prefill(dim3 grid, hipStream_t s, int causal, const void* qkv
   uint16_t* o = (uint16_t*)out;
   constexpr int NT = 64 * G * WPH;
   const CascadeOut co{};
-  if (pk.k) {
+  if (pk.k && pk.f8) {   // FP8 cache (docqa_flash_prefill_paged8: head_dim 128 only)
+    if constexpr (D == 128)
+      flash_prefill_kernel<D, true, true, G, WPH, false, true><<<grid, NT, 0, s>>>(q, row_stride, cu, o, o_stride, Hq, Hkv, scale, pk, co);
+  } else if (pk.k) {
     flash_prefill_kernel<D, true, true, G, WPH><<<grid, NT, 0, s>>>(q, row_stride, cu, o, o_stride, Hq, Hkv, scale, pk, co);
   } else if (causal) {
     flash_prefill_kernel<D, true, false, G, WPH><<<grid, NT, 0, s>>>(q, row_stride, cu, o, o_stride, Hq, Hkv, scale, pk, co);
@@ -443,6 +458,22 @@ int docqa_flash_prefill_paged(const void* qkv, int row_stride, const int* cu_seq
   int log2BS = 0;
   while ((1 << log2BS) < BS) ++log2BS;
   PagedKV pk{(const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables, maxb, ctx_start, BS, log2BS};
+  return prefill_dispatch(s, B, max_len, head_dim, 1, qkv, row_stride, cu_seqlens, out, o_stride, Hq, Hkv,
+                          scale, pk);
+}
+
+// The same over an FP8 (e4m3) cache: the paged gather loads 8 B per lane and widens the codes
+// before the LDS store; everything after the gather is the bf16 kernel.
+int docqa_flash_prefill_paged8(const void* qkv, int row_stride, const int* cu_seqlens, void* out,
+                               int o_stride, int B, int max_len, int Hq, int Hkv, int head_dim,
+                               float scale, const void* k_cache, const void* v_cache,
+                               const int* block_tables, int maxb, const int* ctx_start, int BS,
+                               hipStream_t s) {
+  if (B == 0 || max_len == 0) return 0;
+  if (Hq % Hkv != 0 || (BS & (BS - 1)) != 0 || head_dim != 128) return -1;
+  int log2BS = 0;
+  while ((1 << log2BS) < BS) ++log2BS;
+  PagedKV pk{(const uint16_t*)k_cache, (const uint16_t*)v_cache, block_tables, maxb, ctx_start, BS, log2BS, 1};
   return prefill_dispatch(s, B, max_len, head_dim, 1, qkv, row_stride, cu_seqlens, out, o_stride, Hq, Hkv,
                           scale, pk);
 }

@@ -78,12 +78,33 @@ __device__ __forceinline__ void load_partials(const PT* P, int S, size_t slab, s
   }
 }
 
+// FP8 paged KV (F8): a code is the round-to-nearest-even OCP e4m3 image of the bf16 value the
+// bf16 path stores, clamped to +-448 first so the NaN codes 0x7f / 0xff are never written
+// (v_cvt_pk_fp8_f32 after a v_med3; a NaN input becomes -448, code 0xfe: fmaxf returns the non-NaN operand -- ops.reference.kv_fp8_codes does the same).  4 bf16 -> 4 codes:
+__device__ __forceinline__ uint32_t kv8_codes4(uint2 v) {
+  const float f0 = fminf(fmaxf(__uint_as_float(v.x << 16), -448.f), 448.f);
+  const float f1 = fminf(fmaxf(__uint_as_float(v.x & 0xffff0000u), -448.f), 448.f);
+  const float f2 = fminf(fmaxf(__uint_as_float(v.y << 16), -448.f), 448.f);
+  const float f3 = fminf(fmaxf(__uint_as_float(v.y & 0xffff0000u), -448.f), 448.f);
+  int c = __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, 0, false);
+  c = __builtin_amdgcn_cvt_pk_fp8_f32(f2, f3, c, true);
+  return (uint32_t)c;
+}
+// ... and back: the codes' exact bf16 image (every e4m3 value is a bf16 value), which replaces
+// the rotated K / the V in the packed QKV row so that the un-paged prefill over qkv attends
+// the same values every later paged read of the cache does
+__device__ __forceinline__ uint2 kv8_image4(uint32_t c) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, false);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c, 1.0f, true);
+  return uint2{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b)};
+}
+
 // SPLIT: the packed QKV row comes from a split-K decode projection as S fp32 partial slabs
 // P[s][t][:] and is written (rotated) into `qkv` -- the combine fused into this pass.
 // Grid (T, ceil(heads / heads-per-workgroup)): one head slice per thread and no loop, so
 // a 128-token decode batch is 384 workgroups (Llama-3-8B: 48 heads / 16 per workgroup)
 // instead of 128 workgroups each walking three passes.
-template <bool SPLIT, int NS, typename PT = float>
+template <bool SPLIT, int NS, typename PT = float, bool F8 = false>
 __global__ __launch_bounds__(256) void rope_cache_kernel(
     uint16_t* __restrict__ qkv, const int* __restrict__ positions,
     const float* __restrict__ cos_sin, const int* __restrict__ slot_mapping,
@@ -128,6 +149,21 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(
     uint2 oa, ob;
     oa.x = pack2(o1[0], o1[1]); oa.y = pack2(o1[2], o1[3]);
     ob.x = pack2(o2[0], o2[1]); ob.y = pack2(o2[2], o2[3]);
+    if constexpr (F8) {
+      if (h >= Hq) {   // K head of an FP8 cache: codes to the cache, their image to qkv
+        const uint32_t ca = kv8_codes4(oa), cb = kv8_codes4(ob);
+        *reinterpret_cast<uint2*>(hp + i0) = kv8_image4(ca);
+        *reinterpret_cast<uint2*>(hp + half + i0) = kv8_image4(cb);
+        if (slot >= 0) {
+          const int kh = h - Hq;
+          const int blk = slot / BS, off = slot - blk * BS;
+          uint8_t* dst = reinterpret_cast<uint8_t*>(k_cache) + (((size_t)blk * Hkv + kh) * BS + off) * D;
+          *reinterpret_cast<uint32_t*>(dst + i0) = ca;
+          *reinterpret_cast<uint32_t*>(dst + half + i0) = cb;
+        }
+        return;
+      }
+    }
     *reinterpret_cast<uint2*>(hp + i0) = oa;
     *reinterpret_cast<uint2*>(hp + half + i0) = ob;
     if (h >= Hq && slot >= 0) {
@@ -145,8 +181,22 @@ __global__ __launch_bounds__(256) void rope_cache_kernel(
       vv = pack8(x8);
       *reinterpret_cast<uint4*>(hp + sub * 8) = vv;
     } else {
-      if (slot < 0) return;
+      if (!F8 && slot < 0) return;
       vv = *reinterpret_cast<const uint4*>(hp + sub * 8);
+    }
+    if constexpr (F8) {   // V head of an FP8 cache: codes to the cache, their image to qkv
+      uint2 c;
+      c.x = kv8_codes4(uint2{vv.x, vv.y});
+      c.y = kv8_codes4(uint2{vv.z, vv.w});
+      const uint2 lo = kv8_image4(c.x), hi = kv8_image4(c.y);
+      *reinterpret_cast<uint4*>(hp + sub * 8) = uint4{lo.x, lo.y, hi.x, hi.y};
+      if (slot >= 0) {
+        const int vh = h - Hq - Hkv;
+        const int blk = slot / BS, off = slot - blk * BS;
+        uint8_t* dst = reinterpret_cast<uint8_t*>(v_cache) + (((size_t)blk * Hkv + vh) * BS + off) * D;
+        *reinterpret_cast<uint2*>(dst + sub * 8) = c;
+      }
+      return;
     }
     if (slot >= 0) {
       const int vh = h - Hq - Hkv;
@@ -174,7 +224,20 @@ int docqa_rope_cache(void* qkv, const int* positions, const float* cos_sin,
   return 0;
 }
 
-template <typename PT>
+// the same into an FP8 (e4m3) cache: codes to k_cache / v_cache, their bf16 image to qkv
+int docqa_rope_cache8(void* qkv, const int* positions, const float* cos_sin, const int* slot_mapping,
+                      void* k_cache, void* v_cache, int T, int Hq, int Hkv, int D, int row_stride, int BS,
+                      hipStream_t s) {
+  if (T == 0) return 0;
+  if (D % 8 != 0 || (256 % (D / 8)) != 0 || !slot_mapping) return -1;
+  rope_cache_kernel<false, 0, float, true><<<rope_grid(T, Hq, Hkv, D), 256, 0, s>>>(
+      (uint16_t*)qkv, positions, cos_sin, slot_mapping, (uint16_t*)k_cache, (uint16_t*)v_cache,
+      Hq, Hkv, D, row_stride, BS, nullptr, 0, 0);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename PT, bool F8 = false>
 static int rope_cache_splitk_any(const PT* P, int S, void* qkv_out, const int* positions, const float* cos_sin,
                                  const int* slot_mapping, void* k_cache, void* v_cache, int T, int Hq, int Hkv,
                                  int D, int row_stride, int BS, hipStream_t s) {
@@ -183,9 +246,9 @@ static int rope_cache_splitk_any(const PT* P, int S, void* qkv_out, const int* p
   const dim3 grid = rope_grid(T, Hq, Hkv, D);
   const size_t slab = (size_t)T * row_stride;
   uint16_t *q = (uint16_t*)qkv_out, *kc = (uint16_t*)k_cache, *vc = (uint16_t*)v_cache;
-#define DOCQA_ROPE_SPLIT(NS_)                                                                      \
-  rope_cache_kernel<true, NS_, PT><<<grid, 256, 0, s>>>(q, positions, cos_sin, slot_mapping, kc, vc, \
-                                                        Hq, Hkv, D, row_stride, BS, P, S, slab)
+#define DOCQA_ROPE_SPLIT(NS_)                                                                          \
+  rope_cache_kernel<true, NS_, PT, F8><<<grid, 256, 0, s>>>(q, positions, cos_sin, slot_mapping, kc, vc, \
+                                                            Hq, Hkv, D, row_stride, BS, P, S, slab)
   switch (S) {
     case 1: DOCQA_ROPE_SPLIT(1); break;
     case 2: DOCQA_ROPE_SPLIT(2); break;
@@ -220,6 +283,18 @@ int docqa_rope_cache_splitk16(const void* P, int S, void* qkv_out, const int* po
                                T, Hq, Hkv, D, row_stride, BS, s);
 }
 
+// split-K slabs (fp32, or bf16 with slab16) into an FP8 (e4m3) cache
+int docqa_rope_cache_splitk8(const void* P, int slab16, int S, void* qkv_out, const int* positions,
+                             const float* cos_sin, const int* slot_mapping, void* k_cache, void* v_cache, int T,
+                             int Hq, int Hkv, int D, int row_stride, int BS, hipStream_t s) {
+  if (!slot_mapping) return -1;
+  if (slab16)
+    return rope_cache_splitk_any<uint16_t, true>((const uint16_t*)P, S, qkv_out, positions, cos_sin, slot_mapping,
+                                                 k_cache, v_cache, T, Hq, Hkv, D, row_stride, BS, s);
+  return rope_cache_splitk_any<float, true>((const float*)P, S, qkv_out, positions, cos_sin, slot_mapping, k_cache,
+                                            v_cache, T, Hq, Hkv, D, row_stride, BS, s);
+}
+
 // Token-granular prefix reuse (engine/kv_cache.py TailCache): copy K/V rows [0, m) of a
 // source block into the same rows of a destination block, for every layer and both K and
 // V, in ONE launch (the per-layer tensor-indexing copies were 64 launches of ~40 us).
@@ -241,6 +316,33 @@ __global__ __launch_bounds__(256) void kv_copy_rows_kernel(const uint64_t* __res
     const size_t dso = (((size_t)dst * Hkv + h) * BS + r) * D + ch * 8;
     *reinterpret_cast<uint4*>(base + dso) = *reinterpret_cast<const uint4*>(base + so);
   }
+}
+
+// the same over 1-byte elements (FP8 cache): a row is D bytes, D / 16 16-B chunks
+__global__ __launch_bounds__(256) void kv_copy_rows8_kernel(const uint64_t* __restrict__ caches,
+                                                            const int* __restrict__ tab, int nblocks, int Hkv,
+                                                            int BS, int D) {
+  const int c = blockIdx.x;
+  uint8_t* base = reinterpret_cast<uint8_t*>(caches[blockIdx.y]);
+  const int src = tab[3 * c], dst = tab[3 * c + 1], m = tab[3 * c + 2];
+  if (src < 0 || src >= nblocks || dst < 0 || dst >= nblocks || m <= 0 || m > BS) return;
+  const int cpr = D / 16;
+  const int total = Hkv * m * cpr;
+  for (int i = threadIdx.x; i < total; i += blockDim.x) {
+    const int ch = i % cpr, r = (i / cpr) % m, h = i / (cpr * m);
+    const size_t so = (((size_t)src * Hkv + h) * BS + r) * D + ch * 16;
+    const size_t dso = (((size_t)dst * Hkv + h) * BS + r) * D + ch * 16;
+    *reinterpret_cast<uint4*>(base + dso) = *reinterpret_cast<const uint4*>(base + so);
+  }
+}
+
+int docqa_kv_copy_rows8(const uint64_t* caches, int ntensors, const int* tab, int n, int nblocks, int Hkv, int BS,
+                        int D, hipStream_t s) {
+  if (n == 0 || ntensors == 0) return 0;
+  if (D % 16 != 0 || BS <= 0 || Hkv <= 0 || ntensors > 65535) return -1;
+  kv_copy_rows8_kernel<<<dim3(n, ntensors), 256, 0, s>>>(caches, tab, nblocks, Hkv, BS, D);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
 }
 
 int docqa_kv_copy_rows(const uint64_t* caches, int ntensors, const int* tab, int n, int nblocks, int Hkv, int BS,

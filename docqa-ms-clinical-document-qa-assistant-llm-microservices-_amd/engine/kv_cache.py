@@ -11,6 +11,8 @@ and by the pure-Python :class:`PyBlockAllocator` otherwise.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 
@@ -76,16 +78,36 @@ class KVCache:
 
     @staticmethod
     def bytes_per_block(layers, kv_heads, head_dim, block_size, dtype_bytes=2) -> int:
+        """``dtype_bytes``: bytes per element, or the cache dtype (1 for an FP8 cache)."""
+        if isinstance(dtype_bytes, torch.dtype):
+            dtype_bytes = dtype_bytes.itemsize
         return 2 * layers * kv_heads * head_dim * block_size * dtype_bytes
 
     @classmethod
     def for_budget(cls, layers, kv_heads, head_dim, budget_bytes, block_size=64, device="cuda",
                    dtype=torch.bfloat16):
-        nb = max(1, budget_bytes // cls.bytes_per_block(layers, kv_heads, head_dim, block_size))
+        nb = max(1, budget_bytes // cls.bytes_per_block(layers, kv_heads, head_dim, block_size, dtype))
         return cls(layers, int(nb), kv_heads, head_dim, block_size, device, dtype)
 
     def blocks_for(self, tokens: int) -> int:
         return (tokens + self.block_size - 1) // self.block_size
+
+
+KV_DTYPES = ("bf16", "fp8")
+
+
+def resolve_kv_dtype(kv_dtype, model_dtype):
+    """The cache dtype of ``kv_dtype``: None (env DOCQA_KV_CACHE, default ``bf16``), ``"bf16"``
+    (the model's dtype), ``"fp8"`` (OCP e4m3 codes without scales), or one of those two as a
+    torch dtype -- any other dtype would only fail later, at a kernel's cache dtype check."""
+    if isinstance(kv_dtype, torch.dtype):
+        if kv_dtype not in (model_dtype, torch.float8_e4m3fn):
+            raise ValueError(f"kv_dtype must be the model dtype {model_dtype} or torch.float8_e4m3fn, got {kv_dtype}")
+        return kv_dtype
+    name = (os.environ.get("DOCQA_KV_CACHE", "bf16") if kv_dtype is None else str(kv_dtype)).strip().lower()
+    if name not in KV_DTYPES:
+        raise ValueError(f"DOCQA_KV_CACHE / kv_dtype must be one of {KV_DTYPES}, got {name!r}")
+    return torch.float8_e4m3fn if name == "fp8" else model_dtype
 
 
 def chain_keys(tokens, block_size: int, nblocks: int) -> list[int]:

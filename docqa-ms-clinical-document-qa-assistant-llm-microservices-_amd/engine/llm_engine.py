@@ -30,7 +30,7 @@ from .. import ops
 from ..parallel import comm
 from ..utils import tracing
 from ..models.llama import AttnMeta, LlamaModel
-from .kv_cache import KVCache, TailCache, chain_keys
+from .kv_cache import KVCache, TailCache, chain_keys, resolve_kv_dtype
 
 _PREFILL_LOG = os.environ.get("DOCQA_PREFILL_LOG") == "1"   # one JSON line per prefill chunk
 _PREFILL_DUMP = os.environ.get("DOCQA_PREFILL_DUMP", "")       # dir: save paged-prefill shapes for replay
@@ -312,14 +312,24 @@ class LLMEngine:
     def __init__(self, model: LlamaModel, max_batch: int = 64, max_context: int = 2048,
                  block_size: int = 64, num_blocks: int | None = None, use_graphs: bool = True,
                  max_prefill_tokens: int = 65536, prefix_cache: bool = True,
-                 kv_mem_fraction: float | None = None):
+                 kv_mem_fraction: float | None = None, kv_dtype: str | None = None):
         """``num_blocks``: KV pool size; default ``max_batch`` full-context sequences, or --
         with ``kv_mem_fraction`` (env DOCQA_KV_MEM_FRACTION) on a GPU -- that fraction of the
         HBM still free after the weights, minus the prefill activation headroom (the block
-        prefix cache keeps every block the running batches do not need)."""
+        prefix cache keeps every block the running batches do not need).
+        ``kv_dtype``: ``"bf16"`` | ``"fp8"`` (default: env DOCQA_KV_CACHE, else ``bf16``) -- FP8
+        stores K/V as OCP e4m3 codes without scales: half the bytes per block (twice the blocks
+        for one ``kv_mem_fraction``) and half the K/V bytes a decode step streams."""
         self.model = model
         self.cfg = model.cfg
         self.device = model.device
+        self.kv_dtype = resolve_kv_dtype(kv_dtype, model.dtype)
+        self.kv_fp8 = self.kv_dtype == ops.KV_FP8
+        if (self.kv_fp8 and self.device.type == "cuda"
+                and not ops.kv_fp8_shape_ok(model.hq, model.hkv, model.cfg.head_dim, block_size)):
+            raise ValueError("FP8 KV cache on the GPU: head_dim 128, block_size 64 and 4 or 8 query heads per "
+                             f"KV head (got head_dim {model.cfg.head_dim}, block_size {block_size}, "
+                             f"{model.hq} / {model.hkv} heads)")
         self.max_batch = max_batch
         self.block_size = block_size
         self.max_blocks_per_seq = (max_context + block_size - 1) // block_size
@@ -357,7 +367,7 @@ class LLMEngine:
                                       f"one {self.max_context}-token sequence needs {self.max_blocks_per_seq + 1}")
         num_blocks = self._agree_across_tp(model, num_blocks)
         self.kv = KVCache(self.cfg.layers, num_blocks, model.hkv, self.cfg.head_dim, block_size,
-                          self.device, model.dtype)
+                          self.device, self.kv_dtype)
         self.use_graphs = use_graphs and self.device.type == "cuda"
         # TunableOp search for the decode buckets' library GEMMs (only the LM head below the
         # mid-M rows is left on hipBLASLt): off by default -- ~28 s of service start-up for no
@@ -407,7 +417,7 @@ class LLMEngine:
         cfg = model.cfg
         free, _ = torch.cuda.mem_get_info(self.device)
         el = torch.finfo(model.dtype).bits // 8
-        block_bytes = cfg.layers * 2 * model.hkv * block_size * cfg.head_dim * el
+        block_bytes = KVCache.bytes_per_block(cfg.layers, model.hkv, cfg.head_dim, block_size, self.kv_dtype)
         # prefill activations at the token budget (hidden-sized buffers, QKV, the gate|up
         # product / SwiGLU output) twice over, + 6 GB for graph pools, workspaces and the index
         per_tok = (6 * cfg.hidden + (model.hq + 2 * model.hkv) * cfg.head_dim + 3 * model.inter) * el
@@ -508,6 +518,10 @@ class LLMEngine:
                 meta.decode_defer = g.groups.dim() == 3 and _defer_groups_on()
                 meta.decode_inline = (g.groups.dim() == 3 and g.groups.shape[0] == 2 and _inline_prefix_on()
                                       and not _defer_groups_on())
+            if self.kv_fp8 and self.device.type == "cuda" and not meta.decode_inline:
+                # FP8 cache: no shared-prefix kernel -- anything but the inline split plan
+                # attends per row
+                meta.shared_table = meta.shared_len = meta.decode_groups = None
         return meta
 
     def _select(self, logits, g: _DecodeGraph):
@@ -660,6 +674,7 @@ class LLMEngine:
         return (B >= _GROUP_NOPREFIX_MIN and _GROUP_NOPREFIX and self.group_decode and self.cascade and fit
                 and self.device.type == "cuda" and _split_groups_on() and _inline_prefix_on()
                 and not _defer_groups_on() and not _persist_groups_on()
+                and (not self.kv_fp8 or _group_wave_on())     # FP8 cache: the wave kernel only
                 and ops.grouped_decode_ok(self.kv.caches[0][0], torch.empty(0, self.max_blocks_per_seq),
                                           self.model.hq, max_blocks=ops.GROUP_MAX_BLOCKS))
 

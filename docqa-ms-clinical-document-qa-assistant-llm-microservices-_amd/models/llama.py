@@ -348,6 +348,10 @@ class LlamaModel:
         # (comm.tp_add_rmsnorm); split 0 = library GEMM + plain consumer.  Prefill (large M):
         # the 256 x 256 MFMA GEMM (pgemm.hip) with SwiGLU fused into the gate|up epilogue.
         decode = not meta.prefill
+        # an FP8 KV cache is written by rope_cache / rope_cache_splitk only: the attention
+        # kernels that fuse RoPE and the new token's cache write store bf16
+        kv8 = bool(kv_caches) and ops.kv_is_fp8(kv_caches[0][0])
+        group_fused, cascade_rope = _GROUP_FUSED and not kv8, _CASCADE_ROPE and not kv8
         lin = ops.decode_linear if decode else ops.prefill_linear
         M = x.shape[0]
         plans = {}
@@ -372,7 +376,7 @@ class LlamaModel:
             # that read QKV slabs themselves take fp32 only
             s16 = x.is_cuda and self.tp == 1 and ops.SLAB_BF16
             qkv_rope = (not decode or
-                        (not (meta.decode_groups is not None and meta.decode_inline and _GROUP_FUSED
+                        (not (meta.decode_groups is not None and meta.decode_inline and group_fused
                               and meta.slot_mapping is not None) if cascade
                          else not (meta.block_tables is not None and kv_caches
                                    and ops.fused_decode_ok(kv_caches[0][0], meta.block_tables))))
@@ -500,7 +504,7 @@ class LlamaModel:
             if cascade:
                 # shared-prefix decode: RoPE + cache write, then prefix-once + suffix attention
                 if (sq and meta.decode_groups is not None and meta.decode_inline and x.is_cuda
-                        and _GROUP_FUSED and meta.slot_mapping is not None):
+                        and group_fused and meta.slot_mapping is not None):
                     # the group kernel reads the QKV slabs itself (RoPE + new-token cache write)
                     a = ops.paged_decode_grouped_fused(qkv_slabs, meta.positions, self.cos_sin, meta.slot_mapping,
                                                        kc, vc, meta.block_tables, meta.context_lens, hq,
@@ -520,7 +524,7 @@ class LlamaModel:
                         a = ops.paged_decode_cascade(qkv, kc, vc, meta.block_tables, meta.context_lens, hq,
                                                      meta.max_context, self.scale, meta.shared_table,
                                                      meta.shared_len, meta.cascade_chunks, meta.seq_order)
-                elif not _CASCADE_ROPE:
+                elif not cascade_rope:
                     qkv = lin(x, L["qkv"])
                     ops.rope_cache(qkv, meta.positions, self.cos_sin, meta.slot_mapping, kc, vc, hq, hkv, D)
                     if meta.decode_groups is not None:

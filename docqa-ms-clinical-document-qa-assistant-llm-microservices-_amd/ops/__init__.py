@@ -939,9 +939,26 @@ def decode_ticket(n: int, device) -> torch.Tensor | None:
     return torch.zeros(n, dtype=torch.int32, device=device)
 
 
+KV_FP8 = ref.KV_FP8     # dtype of an FP8 paged KV cache (OCP e4m3 codes, no scales)
+kv_fp8_codes = ref.kv_fp8_codes
+
+
+def kv_is_fp8(k_cache) -> bool:
+    return k_cache.dtype == KV_FP8
+
+
+def kv_fp8_shape_ok(Hq: int, Hkv: int, D: int, BS: int) -> bool:
+    """Shapes the FP8-KV kernels cover on the GPU: head_dim 128, 64-token blocks, 4 or 8 query
+    heads per KV head."""
+    return D == 128 and BS == 64 and Hkv > 0 and Hq in (4 * Hkv, 8 * Hkv)
+
+
 def fused_decode_ok(k_cache, block_tables) -> bool:
     """Shapes the fused decode attention kernel supports (head_dim 128, 64-token blocks,
-    <= 256 blocks per sequence)."""
+    <= 256 blocks per sequence; bf16 caches only -- an FP8 cache takes rope_cache_splitk +
+    paged_decode)."""
+    if kv_is_fp8(k_cache):
+        return False
     return k_cache.shape[2] == 64 and k_cache.shape[3] == 128 and block_tables.shape[1] <= 256
 
 
@@ -952,7 +969,8 @@ def rope_cache_splitk(P, positions, cos_sin, slot_mapping, k_cache, v_cache, Hq,
             k_cache = v_cache = P
         return _native().rope_cache_splitk(P, positions, cos_sin, slot_mapping, k_cache, v_cache, Hq, Hkv, D)
     # the model dtype: bf16 on the GPU path, fp32 for CPU reference models
-    qkv = P.float().sum(0).to(k_cache.dtype if slot_mapping is not None else torch.bfloat16)
+    dt = k_cache.dtype if slot_mapping is not None and not kv_is_fp8(k_cache) else torch.bfloat16
+    qkv = P.float().sum(0).to(dt)
     ref.rope_cache(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, Hq, Hkv, D)
     return qkv
 
@@ -1056,6 +1074,8 @@ def cascade_ok(k_cache, block_tables, Hq: int) -> bool:
     reference path takes any GQA shape)."""
     if not _gpu(k_cache):
         return Hq % k_cache.shape[1] == 0
+    if kv_is_fp8(k_cache):
+        return False        # the shared-prefix kernels read bf16 caches only
     return (k_cache.shape[2] == 64 and k_cache.shape[3] == 128 and Hq == 4 * k_cache.shape[1]
             and block_tables.shape[1] <= 256)
 
@@ -1143,6 +1163,11 @@ def grouped_decode_ok(k_cache, block_tables, Hq: int, max_blocks: int | None = N
     ``max_blocks``, the most any row of the batch reaches by the end of its decode, or else
     the block table's width (its capacity)."""
     nb = block_tables.shape[1] if max_blocks is None else max_blocks
+    if _gpu(k_cache) and kv_is_fp8(k_cache):
+        # FP8 cache: only the wave-parallel split kernel with the plan built from block 0
+        # (``inline_prefix``) reads it -- the caller must hold a [2, cap, 8] split plan
+        return (k_cache.shape[2] == 64 and k_cache.shape[3] == 128 and Hq == 4 * k_cache.shape[1]
+                and block_tables.shape[1] <= 256 and nb <= GROUP_MAX_BLOCKS)
     return cascade_ok(k_cache, block_tables, Hq) and nb <= GROUP_MAX_BLOCKS
 
 
@@ -1217,12 +1242,15 @@ def kv_copy_rows(pools: list, copies: list, ptrs: torch.Tensor | None = None) ->
         if ptrs is None:
             ptrs = torch.tensor([t.data_ptr() for kv in pools for t in kv], dtype=torch.int64, device=k0.device)
         tab = torch.tensor(copies, dtype=torch.int32).pin_memory().to(k0.device, non_blocking=True)
-        _native().kv_copy_rows(ptrs, tab, k0.shape[0], k0.shape[1], k0.shape[2], k0.shape[3])
+        copy = _native().kv_copy_rows8 if kv_is_fp8(k0) else _native().kv_copy_rows   # 1-byte / bf16 rows
+        copy(ptrs, tab, k0.shape[0], k0.shape[1], k0.shape[2], k0.shape[3])
         return
     src = torch.tensor([s for s, _, m in copies for _ in range(m)], dtype=torch.long, device=k0.device)
     dst = torch.tensor([d for _, d, m in copies for _ in range(m)], dtype=torch.long, device=k0.device)
     rows = torch.tensor([i for _, _, m in copies for i in range(m)], dtype=torch.long, device=k0.device)
     for kc, vc in pools:
+        if kv_is_fp8(kc):   # an FP8 pool is copied through its code bytes
+            kc, vc = kc.view(torch.uint8), vc.view(torch.uint8)
         kc[dst, :, rows] = kc[src, :, rows]
         vc[dst, :, rows] = vc[src, :, rows]
 

@@ -92,10 +92,37 @@ def rope_cache(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, Hq, Hkv,
         valid = sm >= 0
         sm = sm[valid]
         blk, off = sm // BS, sm % BS
+        if k_cache.dtype == KV_FP8:
+            # FP8 KV cache: the codes are the e4m3 image of the bf16 values the bf16 path would
+            # have stored, and the rotated K and the V left in ``qkv`` become the codes' exact
+            # image -- the un-paged prefill over ``qkv`` and every paged read attend one model
+            kv8 = kv_fp8_codes(x[:, Hq:])
+            x[:, Hq:] = kv8.to(qkv.dtype)
+            bits = kv8.view(torch.uint8)       # indexing on the code bytes (any device)
+            k_cache.view(torch.uint8)[blk, :, off] = bits[valid, :Hkv]
+            v_cache.view(torch.uint8)[blk, :, off] = bits[valid, Hkv:]
+            return
         k = x[valid, Hq : Hq + Hkv]
         v = x[valid, Hq + Hkv :]
         k_cache[blk, :, off] = k
         v_cache[blk, :, off] = v
+
+
+KV_FP8 = torch.float8_e4m3fn   # the FP8 paged-KV format: OCP e4m3 codes, no scales
+
+
+def _kv_gather(cache, blocks):
+    """cache[blocks]; an FP8 cache is indexed through its code bytes."""
+    if cache.dtype == KV_FP8:
+        return cache.view(torch.uint8)[blocks].view(KV_FP8)
+    return cache[blocks]
+
+
+def kv_fp8_codes(x):
+    """e4m3 codes of K/V values: clamped to +-448 first (the NaN codes 0x7f / 0xff are never
+    produced), then round-to-nearest-even.  A NaN input becomes -448 (code 0xfe), as in the
+    kernel, whose ``fminf(fmaxf(x, -448), 448)`` returns the non-NaN operand."""
+    return torch.nan_to_num(x.float(), nan=-448.0).clamp(-448.0, 448.0).to(KV_FP8)
 
 
 def silu_mul(gu, interleaved: bool = False):
@@ -227,8 +254,8 @@ def paged_decode(q, k_cache, v_cache, block_tables, context_lens, Hq, max_contex
         L = int(context_lens[b])
         nblk = (L + BS - 1) // BS
         blocks = block_tables[b, :nblk].long()
-        k = k_cache[blocks].permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :L].float()
-        v = v_cache[blocks].permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :L].float()
+        k = _kv_gather(k_cache, blocks).permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :L].float()
+        v = _kv_gather(v_cache, blocks).permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :L].float()
         qb = q[b, : Hq * D].view(Hkv, G, D).float()
         s = torch.einsum("hgd,htd->hgt", qb, k) * scale
         p = torch.softmax(s, -1)
@@ -246,8 +273,8 @@ def paged_decode_cascade(q, k_cache, v_cache, block_tables, context_lens, Hq, ma
     G = Hq // Hkv
     P = int(prefix_len.reshape(-1)[0])
     pb = prefix_table.reshape(-1)[: P // BS].long()
-    kp = k_cache[pb].permute(1, 0, 2, 3).reshape(Hkv, -1, D).float()
-    vp = v_cache[pb].permute(1, 0, 2, 3).reshape(Hkv, -1, D).float()
+    kp = _kv_gather(k_cache, pb).permute(1, 0, 2, 3).reshape(Hkv, -1, D).float()
+    vp = _kv_gather(v_cache, pb).permute(1, 0, 2, 3).reshape(Hkv, -1, D).float()
     out = torch.zeros(B, Hq * D, dtype=q.dtype, device=q.device)
     for b in range(B):
         L = int(context_lens[b])
@@ -255,8 +282,8 @@ def paged_decode_cascade(q, k_cache, v_cache, block_tables, context_lens, Hq, ma
             continue
         nblk = (L + BS - 1) // BS
         blocks = block_tables[b, P // BS:nblk].long()
-        ks = k_cache[blocks].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, : L - P].float()
-        vs = v_cache[blocks].permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, : L - P].float()
+        ks = _kv_gather(k_cache, blocks).permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, : L - P].float()
+        vs = _kv_gather(v_cache, blocks).permute(1, 0, 2, 3).reshape(Hkv, -1, D)[:, : L - P].float()
         k, v = torch.cat([kp, ks], 1), torch.cat([vp, vs], 1)
         qb = q[b, : Hq * D].view(Hkv, G, D).float()
         p = torch.softmax(torch.einsum("hgd,htd->hgt", qb, k) * scale, -1)
@@ -306,8 +333,8 @@ def flash_prefill_paged(qkv, cu_seqlens, max_len, Hq, Hkv, D, scale, k_cache, v_
         Lk = P0 + L
         nblk = (Lk + BS - 1) // BS
         blocks = block_tables[b, :nblk].long()
-        k = k_cache[blocks].permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :Lk].float()
-        v = v_cache[blocks].permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :Lk].float()
+        k = _kv_gather(k_cache, blocks).permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :Lk].float()
+        v = _kv_gather(v_cache, blocks).permute(1, 0, 2, 3).reshape(Hkv, nblk * BS, D)[:, :Lk].float()
         k = k.repeat_interleave(G, 0)
         v = v.repeat_interleave(G, 0)
         q = x[s0:s1, :Hq].float().transpose(0, 1)

@@ -204,6 +204,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--llm-weights", choices=("bf16", "fp8"), default=None,
                     help="generator weight format (DOCQA_LLM_WEIGHTS): fp8 streams per-row e4m3 weights in "
                          "decode steps of up to 32 rows where measured faster (TP = 1)")
+    ap.add_argument("--kv-cache", choices=("bf16", "fp8"), default=None,
+                    help="paged KV cache format (DOCQA_KV_CACHE): fp8 stores K/V as e4m3 codes -- half the "
+                         "bytes per block, twice the blocks for one DOCQA_KV_MEM_FRACTION")
     ap.add_argument("--embed", default="minilm-l6")
     ap.add_argument("--real-synthese", action="store_true")
     ap.add_argument("--services", default="", help="comma list of ingest,deid,indexer,qa,synthese,ui (default all)")
@@ -230,6 +233,8 @@ def main() -> None:
     if a.llm_weights is not None:
         # before any worker / supervised child is spawned: they inherit the environment
         os.environ["DOCQA_LLM_WEIGHTS"] = a.llm_weights
+    if a.kv_cache is not None:
+        os.environ["DOCQA_KV_CACHE"] = a.kv_cache
 
     # The HTTP front end (uvicorn thread), the QA prep thread and the engine's scheduler
     # thread share one GIL; at CPython's 5 ms switch interval each request's few GIL hand-
