@@ -85,7 +85,8 @@ class Settings:
     # llm-qa
     llm_model: str = field(default_factory=lambda: os.getenv("LLM_MODEL", "llama3-8b"))
     # generator weight format: bf16 | fp8 (per-row e4m3 copies streamed by one-row decode steps,
-    # models/llama.py quantize_fp8; read by models/checkpoint.py resolve_llama)
+    # models/llama.py quantize_fp8) | mxfp4 (OCP 4-bit block-scaled copies streamed by one-row decode
+    # steps, quantize_mxfp4; lossier than fp8); read by models/checkpoint.py resolve_llama
     llm_weights: str = field(default_factory=lambda: os.getenv("DOCQA_LLM_WEIGHTS", "bf16"))
     # paged KV cache format: bf16 | fp8 (e4m3 codes without scales: half the bytes per block;
     # read by engine/llm_engine.py LLMEngine(kv_dtype=None))

@@ -1084,6 +1084,74 @@ std::tuple<at::Tensor, at::Tensor> gemv8_argmax_val(const at::Tensor& x, const a
   return {out, outv};
 }
 
+// batch-1 GEMV over MXFP4 weights (dgemm.hip gemv4_kernel): q [N, K / 2] uint8 pairs of OCP e2m1
+// codes, e [N, K / 32] uint8 e8m0 block scales; lb codes per lane per load, kw waves along K
+static int check_mx4w(const at::Tensor& q, const at::Tensor& e, const char* op) {
+  TORCH_CHECK(q.is_cuda() && e.is_cuda(), op, ": q and e must be GPU tensors");
+  TORCH_CHECK(q.is_contiguous() && e.is_contiguous(), op, ": q and e must be contiguous");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15u) == 0, op,
+              ": q must be 16-byte aligned (storage offset a multiple of 16 bytes)");
+  TORCH_CHECK(q.dim() == 2 && q.scalar_type() == at::kByte, op, ": q must be uint8 [N, K / 2]");
+  const int64_t K = q.size(1) * 2;
+  TORCH_CHECK(K % 32 == 0, op, ": K must be a multiple of the 32-element scale block");
+  TORCH_CHECK(e.dim() == 2 && e.scalar_type() == at::kByte && e.size(0) == q.size(0) && e.size(1) == K / 32, op,
+              ": e must be uint8 [N, K / 32]");
+  return (int)K;
+}
+
+at::Tensor gemv4(const at::Tensor& x, const at::Tensor& q, const at::Tensor& e, int64_t splits, int64_t rows,
+                 int64_t lb, int64_t kw, bool glu) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_ALIGN16(x);
+  const int K = check_mx4w(q, e, "gemv4"), N = q.size(0);
+  TORCH_CHECK(x.size(-1) == K && x.numel() == K, "gemv4: one row, K mismatch");
+  TORCH_CHECK(splits >= 1, "gemv4: splits >= 1");
+  c10::DeviceGuard g(x.device());
+  at::Tensor out = glu ? at::empty({1, N / 2}, x.options()) : at::empty({splits, 1, N}, x.options().dtype(at::kFloat));
+  CHECK_RC(docqa_gemv4(x.data_ptr(), q.data_ptr(), e.data_ptr(), glu ? out.data_ptr() : nullptr,
+                       glu ? nullptr : out.data_ptr<float>(), N, K, (int)splits, (int)rows, (int)lb, (int)kw,
+                       glu ? 1 : 0, nullptr, 0, nullptr, nullptr, nullptr, 0.f, stream()), "gemv4");
+  return out;
+}
+
+at::Tensor gemv4_xn(const at::Tensor& Pin, const at::Tensor& res_in, at::Tensor res_out, const at::Tensor& gamma,
+                    double eps, const at::Tensor& q, const at::Tensor& e, int64_t splits, int64_t rows, int64_t lb,
+                    int64_t kw, bool glu) {
+  CHECK_GPU(Pin); CHECK_CONTIG(Pin); CHECK_ALIGN16(Pin); CHECK_BF16(res_in); CHECK_BF16(res_out); CHECK_BF16(gamma);
+  CHECK_CONTIG(res_in); CHECK_CONTIG(res_out); CHECK_CONTIG(gamma);
+  CHECK_ALIGN16(res_in); CHECK_ALIGN16(res_out); CHECK_ALIGN16(gamma);
+  const int K = check_mx4w(q, e, "gemv4_xn"), N = q.size(0);
+  TORCH_CHECK(Pin.scalar_type() == at::kFloat && Pin.dim() == 3 && Pin.size(1) == 1, "xn: slabs fp32 [S, 1, K]");
+  TORCH_CHECK(Pin.size(2) == K && res_in.numel() == K && res_out.numel() == K && gamma.numel() == K,
+              "xn: one row of K");
+  TORCH_CHECK(res_in.data_ptr() != res_out.data_ptr(), "xn: res_out must be a second buffer");
+  TORCH_CHECK(splits >= 1, "gemv4_xn: splits >= 1");
+  c10::DeviceGuard g(Pin.device());
+  at::Tensor out = glu ? at::empty({1, N / 2}, res_in.options()) : at::empty({splits, 1, N}, Pin.options());
+  CHECK_RC(docqa_gemv4(nullptr, q.data_ptr(), e.data_ptr(), glu ? out.data_ptr() : nullptr,
+                       glu ? nullptr : out.data_ptr<float>(), N, K, (int)splits, (int)rows, (int)lb, (int)kw,
+                       glu ? 1 : 0, Pin.data_ptr<float>(), Pin.size(0), res_in.data_ptr(), res_out.data_ptr(),
+                       gamma.data_ptr(), (float)eps, stream()), "gemv4_xn");
+  return out;
+}
+
+// batch-1 LM head + greedy pick over MXFP4 weights (dgemm.hip gemv4_kernel EPI_ARGMAX)
+std::tuple<at::Tensor, at::Tensor> gemv4_argmax_val(const at::Tensor& x, const at::Tensor& q, const at::Tensor& e,
+                                                    int64_t n_valid, int64_t rows, int64_t lb, int64_t kw) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_ALIGN16(x);
+  const int K = check_mx4w(q, e, "gemv4_argmax"), N = q.size(0);
+  TORCH_CHECK(x.size(-1) == K && x.numel() == K, "gemv4_argmax: one row");
+  TORCH_CHECK(rows == 16 || rows == 32, "gemv4_argmax: 16 or 32 rows per workgroup");
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({1}, x.options().dtype(at::kLong));
+  auto outv = at::empty({1}, x.options().dtype(at::kFloat));
+  auto ws_v = at::empty({N / rows + 1}, x.options().dtype(at::kFloat));
+  auto ws_i = at::empty({N / rows + 1}, x.options().dtype(at::kInt));
+  CHECK_RC(docqa_gemv4_argmax(x.data_ptr(), q.data_ptr(), e.data_ptr(), out.data_ptr<int64_t>(),
+                              outv.data_ptr<float>(), ws_v.data_ptr<float>(), ws_i.data_ptr<int>(), N, K, (int)rows,
+                              (int)lb, (int)kw, (int)n_valid, stream()), "gemv4_argmax");
+  return {out, outv};
+}
+
 // 2..32-row decode projections over FP8 weights (dgemm.hip dgemm8_kernel); a shape without an
 // instantiation launches nothing and raises, naming the op
 static int dgemm8_rows(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, const char* op) {
@@ -1672,6 +1740,11 @@ TORCH_LIBRARY(docqa, m) {
   m.def("mgemm_argmax(Tensor x, Tensor w, int n_valid, int cfg=0) -> Tensor");
   m.def("dgemm_argmax_val(Tensor x, Tensor w, int n_valid) -> (Tensor, Tensor)");
   m.def("gemv_argmax_val(Tensor x, Tensor w, int n_valid) -> (Tensor, Tensor)");
+  m.def("gemv4(Tensor x, Tensor q, Tensor e, int splits=1, int rows=16, int lb=32, int kw=1, bool glu=False) -> Tensor");
+  m.def("gemv4_xn(Tensor Pin, Tensor res_in, Tensor(a!) res_out, Tensor gamma, float eps, Tensor q, Tensor e, "
+        "int splits=1, int rows=16, int lb=32, int kw=1, bool glu=False) -> Tensor");
+  m.def("gemv4_argmax_val(Tensor x, Tensor q, Tensor e, int n_valid, int rows=16, int lb=32, int kw=1) "
+        "-> (Tensor, Tensor)");
   m.def("gemv8(Tensor x, Tensor q, Tensor scale, int splits=1, int rows=16, int lb=8, bool glu=False) -> Tensor");
   m.def("gemv8_xn(Tensor Pin, Tensor res_in, Tensor(a!) res_out, Tensor gamma, float eps, Tensor q, Tensor scale, "
         "int splits=1, int rows=16, int lb=8, bool glu=False) -> Tensor");
@@ -1770,6 +1843,9 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("fp32_gemm_nt", &fp32_gemm_nt);
   m.impl("dgemm_argmax_val", &dgemm_argmax_val);
   m.impl("gemv_argmax_val", &gemv_argmax_val);
+  m.impl("gemv4", &gemv4);
+  m.impl("gemv4_xn", &gemv4_xn);
+  m.impl("gemv4_argmax_val", &gemv4_argmax_val);
   m.impl("gemv8", &gemv8);
   m.impl("gemv8_xn", &gemv8_xn);
   m.impl("gemv8_argmax_val", &gemv8_argmax_val);

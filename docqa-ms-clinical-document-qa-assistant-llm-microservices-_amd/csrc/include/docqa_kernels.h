@@ -187,6 +187,15 @@ int docqa_gemv8(const void* X, const void* Wq, const float* scale, void* Y, floa
                 float eps, hipStream_t s);
 int docqa_gemv8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
                        int* ws_i, int N, int K, int R, int LB, int n_valid, hipStream_t s);
+// batch-1 GEMV over MXFP4 weights (dgemm.hip gemv4_kernel): Wq [N, K / 2] bytes of two OCP e2m1
+// codes (element 2j in bits 0..3), E [N, K / 32] e8m0 block scales; R rows per workgroup, LB codes
+// per lane per load (16 | 32), KW waves along K (1 | 2 | 4); otherwise as docqa_gemv8 /
+// docqa_gemv8_argmax.  -1 (nothing launched) for a shape without an instantiation.
+int docqa_gemv4(const void* X, const void* Wq, const void* E, void* Y, float* P, int N, int K, int S, int R, int LB,
+                int KW, int epi, const float* Pin, int Sin, const void* res_in, void* res_out, const void* gamma,
+                float eps, hipStream_t s);
+int docqa_gemv4_argmax(const void* X, const void* Wq, const void* E, int64_t* out, float* outv, float* ws_v,
+                       int* ws_i, int N, int K, int R, int LB, int KW, int n_valid, hipStream_t s);
 // 2..32-row decode projections over FP8 weights (dgemm.hip dgemm8_kernel: the LDS-DMA ring over
 // the codes, K slices of whole 1024-deep ring turns): fp32 slabs P [S, M, N] (tile_rows 64),
 // SwiGLU Y [M, N / 2], LM head + greedy pick (ws_v / ws_i: [M, N / 64]).  -1 (nothing launched)

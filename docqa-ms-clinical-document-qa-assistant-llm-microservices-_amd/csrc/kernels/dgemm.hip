@@ -1146,6 +1146,241 @@ int docqa_gemv8_argmax(const void* X, const void* Wq, const float* scale, int64_
 }
 
 // ---------------------------------------------------------------------------------------
+// MXFP4 weight stream for the batch-1 GEMV: the register-streaming design of gemv8_kernel over
+// OCP microscaling weights -- Wq [N, K / 2] bytes of two e2m1 codes (element 2j in bits 0..3,
+// 2j + 1 in bits 4..7) and E [N, K / 32] e8m0 block scales, W'[n, k] = code * 2^(E[n, k / 32] - 127)
+// (exactly the model's resident bf16 weights), so a projection moves 4.25 bits per weight.
+//   * Lane-to-block map: a lane's load is LB = 32 codes (16 B: exactly one scale block) or 16
+//     codes (8 B: two lanes share a block), and KW of the 4 waves split K while the other
+//     4 / KW split the R rows (RW = R KW / 4 rows per wave).  Four bits per weight leave a wave
+//     too few bytes when all four split a 2048..4096-long K, so the short K run KW = 1 | 2 with
+//     whole-block 16-byte loads; a wave's 64 scale bytes of one chunk are contiguous in E
+//     (one byte load per chunk, 64 B per wave).
+//   * Issue order: block scales, the input row (bf16, unless XN builds it in LDS), then RW rows
+//     x C chunks of codes, non-temporal; retired in that order with counted vmcnt waits.
+//   * v_cvt_scalef32_pk_bf16_fp4 widens two codes per instruction with the block scale applied
+//     (the scale operand is the fp32 E << 23: no multiply, nothing left for the epilogue; a code
+//     times a power of two is exact in bf16), v_dot2_f32_bf16 against the packed bf16 input row
+//     accumulates in fp32 -- one conversion and one dot per two weights, the input row never
+//     unpacked; the waves meet in LDS.
+// Epilogues as gemv8_kernel (EPI_PARTIAL slabs, EPI_GLU, EPI_ARGMAX).
+// Shapes: N % R == 0, Ks = K / S = KW C 64 LB, and 2 RW C + C LB / 8 <= 63 loads per lane.
+namespace {
+__device__ __forceinline__ void gload_ubyte(uint32_t& d, const void* p) {
+  asm volatile("global_load_ubyte %0, %1, off" : "=v"(d) : "v"(p) : "memory");
+}
+
+template <int R, int C, int LB, int KW, int EPI, bool XN>
+__global__ __launch_bounds__(256) void gemv4_kernel(const uint16_t* __restrict__ X, const uint8_t* __restrict__ W,
+                                                    const uint8_t* __restrict__ E, uint16_t* __restrict__ Y,
+                                                    float* __restrict__ P, int N, int K, int Ks, XNormIn xn,
+                                                    int* __restrict__ pi = nullptr, int n_valid = 0) {
+  typedef typename Fp8Chunk<LB / 2>::T WT;   // LB / 2 bytes of codes per load
+  constexpr int RW = R * KW / 4;      // rows per wave
+  constexpr int XH = LB / 8;          // 16-byte input-row loads per chunk
+  constexpr int XL = C * XH;
+  constexpr int CK = 64 * LB;         // k covered by one wave-wide chunk
+  static_assert(LB == 16 || LB == 32, "8- or 16-byte code loads");
+  static_assert(KW == 1 || KW == 2 || KW == 4, "waves along K");
+  static_assert((R & (R - 1)) == 0 && R <= 64 && RW >= 1 && RW * 4 == R * KW, "R a power of two, whole rows per wave");
+  static_assert(EPI == EPI_PARTIAL || R % 16 == 0, "GLU / ARGMAX: whole 16-row groups");
+  static_assert(2 * RW * C + XL <= 63, "loads in flight per lane must fit the vmcnt counter");
+  __shared__ __attribute__((aligned(16))) uint16_t sx[XN ? kXnMaxK : 8];
+  __shared__ float red[KW][R];
+  __shared__ float xred[4];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kg = wave % KW, rg = wave / KW;          // this wave's k group and row group
+  const int n0 = blockIdx.x * R, slice = blockIdx.y, kbeg = slice * Ks;
+  const int kw = kbeg + kg * (Ks / KW);              // this wave's k range
+  const int nw = n0 + rg * RW;                       // this wave's first row
+  // issue order: block scales, input row, codes (row-major) -- retired in that order
+  // chunk (r, c) of this lane: row nw + r, k = kw + c * CK + lane * LB .. + LB
+  uint32_t sc[RW][C];
+  const uint8_t* eb = E + (size_t)nw * (K >> 5) + ((kw + lane * LB) >> 5);
+#pragma unroll
+  for (int r = 0; r < RW; ++r)
+#pragma unroll
+    for (int c = 0; c < C; ++c) gload_ubyte(sc[r][c], eb + (size_t)r * (K >> 5) + c * (CK >> 5));
+  bf16x8 xr[XL];
+  if constexpr (!XN) {
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int h = 0; h < XH; ++h) gload16<0>(xr[c * XH + h], X + kw + c * CK + lane * LB + h * 8);
+  }
+  WT w[RW][C];
+  const uint8_t* wb = W + (size_t)nw * (K >> 1) + ((kw + lane * LB) >> 1);
+#pragma unroll
+  for (int r = 0; r < RW; ++r)
+#pragma unroll
+    for (int c = 0; c < C; ++c) gload_fp8_nt<LB / 2>(w[r][c], wb + (size_t)r * (K >> 1) + c * (CK >> 1));
+  if constexpr (XN) {
+    xnorm_prologue(xn, K, kbeg, Ks, blockIdx.x == 0 && blockIdx.y == 0, sx, xred);
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+      for (int h = 0; h < XH; ++h)
+        xr[c * XH + h] = *reinterpret_cast<const bf16x8*>(sx + (kw - kbeg) + c * CK + lane * LB + h * 8);
+  } else {
+#pragma unroll
+    for (int i = 0; i < XL; ++i) wait_vm_reg<RW * C>(xr[i]);
+  }
+  float acc[RW];
+  static_for<0, RW>([&](auto rc) {
+    constexpr int r = decltype(rc)::value;
+    // row r's chunks (and, issued before them, every scale) landed: everything issued after
+    // them is the later rows' C chunks each
+    wait_vm_row<(RW - 1 - r) * C, C>(w[r]);
+    float a = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      wait_vm_reg<(RW - 1 - r) * C>(sc[r][c]);
+      const float scale = __uint_as_float(sc[r][c] << 23);   // e8m0 -> fp32 2^(e - 127)
+#pragma unroll
+      for (int d = 0; d < LB / 8; ++d) {
+        const uint32_t cw = w[r][c][d];                      // 8 codes: k = 8 d .. 8 d + 7 of the chunk
+        const bf16x8 xv = xr[c * XH + d];
+        const bf16x2 w0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cw, scale, 0);
+        const bf16x2 w1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cw, scale, 1);
+        const bf16x2 w2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cw, scale, 2);
+        const bf16x2 w3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(cw, scale, 3);
+        a = __builtin_amdgcn_fdot2_f32_bf16(w0, bf16x2{xv[0], xv[1]}, a, false);
+        a = __builtin_amdgcn_fdot2_f32_bf16(w1, bf16x2{xv[2], xv[3]}, a, false);
+        a = __builtin_amdgcn_fdot2_f32_bf16(w2, bf16x2{xv[4], xv[5]}, a, false);
+        a = __builtin_amdgcn_fdot2_f32_bf16(w3, bf16x2{xv[6], xv[7]}, a, false);
+      }
+    }
+    acc[r] = wave_sum(a);
+  });
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < RW; ++r) red[kg][rg * RW + r] = acc[r];
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  // lane r < R of wave 0: output row n0 + r
+  const int rr = tid & (R - 1);
+  float v = red[0][rr];
+#pragma unroll
+  for (int g = 1; g < KW; ++g) v += red[g][rr];
+  if constexpr (EPI == EPI_PARTIAL) {
+    if (tid < R) P[(size_t)slice * N + n0 + tid] = v;
+  } else if constexpr (EPI == EPI_ARGMAX) {
+    // the R logits (bf16-rounded, as the unfused logits) -> one (value, id) partial per
+    // workgroup at P / pi [blockIdx.x]
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    if (tid < R && n0 + tid < n_valid) {
+      bv = bf2f(f2bf(v));
+      bi = n0 + tid;
+    }
+#pragma unroll
+    for (int o = 1; o < R; o <<= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      argmax_better(bv, bi, ov, oi);
+    }
+    if (tid == 0) {
+      P[blockIdx.x] = bv;
+      pi[blockIdx.x] = bi;
+    }
+  } else {
+    // group g: gate rows 16 g .. 16 g + 7, up rows 16 g + 8 .. 16 g + 15 -> outputs 8 g .. 8 g + 7
+    const int t = tid & (R / 2 - 1), gi = (t >> 3) * 16 + (t & 7);
+    const float g = __shfl(v, gi, 64), u = __shfl(v, gi + 8, 64);
+    if (tid < R / 2) {
+      const float gv = bf2f(f2bf(g)), uv = bf2f(f2bf(u));   // as the bf16 GEMM output
+      Y[(n0 >> 1) + tid] = f2bf(silu_f(gv) * uv);
+    }
+  }
+}
+
+template <int EPI, bool XN>
+int launch_gemv4(int R, int C, int LB, int KW, dim3 grid, hipStream_t s, const uint16_t* x, const uint8_t* w,
+                 const uint8_t* e, uint16_t* y, float* p, int N, int K, int Ks, const XNormIn& xn, int* pi = nullptr,
+                 int nv = 0) {
+#define GEMV4_CASE(RR, CC, LL, WW)                                                                        \
+  if (R == RR && C == CC && LB == LL && KW == WW) {                                                      \
+    gemv4_kernel<RR, CC, LL, WW, EPI, XN><<<grid, 256, 0, s>>>(x, w, e, y, p, N, K, Ks, xn, pi, nv);     \
+    return 0;                                                                                            \
+  }
+  if constexpr (EPI == EPI_PARTIAL) {
+    GEMV4_CASE(16, 1, 32, 1) GEMV4_CASE(32, 1, 32, 1) GEMV4_CASE(8, 1, 32, 2) GEMV4_CASE(16, 1, 32, 2)
+    GEMV4_CASE(16, 2, 32, 1) GEMV4_CASE(8, 1, 16, 4) GEMV4_CASE(8, 1, 16, 2)
+    if constexpr (!XN) {   // K > kXnMaxK: never the in-kernel input row
+      GEMV4_CASE(8, 1, 32, 4) GEMV4_CASE(16, 1, 32, 4) GEMV4_CASE(4, 7, 32, 1) GEMV4_CASE(8, 7, 32, 1)
+      GEMV4_CASE(4, 7, 16, 2)
+    }
+  } else {
+    GEMV4_CASE(16, 1, 32, 1) GEMV4_CASE(32, 1, 32, 1) GEMV4_CASE(16, 1, 32, 2) GEMV4_CASE(32, 1, 32, 2)
+    GEMV4_CASE(16, 2, 32, 1) GEMV4_CASE(16, 1, 16, 4)
+  }
+#undef GEMV4_CASE
+  return -1;
+}
+
+// shared shape rules of the MXFP4 GEMV entry points; C (chunks per lane) out
+bool gemv4_shape(int N, int K, int S, int R, int LB, int KW, int* C) {
+  if (N < 1 || K < 1 || S < 1 || R < 1 || (LB != 16 && LB != 32) || (KW != 1 && KW != 2 && KW != 4) || K % 32 ||
+      K % S || N % R)
+    return false;
+  const int Ks = K / S;
+  if (Ks % (64 * LB * KW)) return false;
+  *C = Ks / (64 * LB * KW);
+  return true;
+}
+}  // namespace
+
+// Batch-1 GEMV over MXFP4 weights (see gemv4_kernel): Wq [N, K / 2] e2m1 code pairs, E [N, K / 32]
+// e8m0 block scales.  epi 0: fp32 slabs P [S, 1, N]; epi 1: SwiGLU Y [1, N / 2] (R % 16 == 0,
+// S = 1).  LB: codes per lane per load (16 | 32), KW: waves along K (1 | 2 | 4).  Pin != null: the
+// input row from the previous projection's slabs.
+// -1 for any shape / (R, C, LB, KW) without an instantiation: nothing is launched.
+int docqa_gemv4(const void* X, const void* Wq, const void* E, void* Y, float* P, int N, int K, int S, int R, int LB,
+                int KW, int epi, const float* Pin, int Sin, const void* res_in, void* res_out, const void* gamma,
+                float eps, hipStream_t s) {
+  int C = 0;
+  if (!gemv4_shape(N, K, S, R, LB, KW, &C) || !Wq || !E || !docqa_aligned16(Wq)) return -1;
+  const int Ks = K / S;
+  const bool xnm = Pin != nullptr;
+  const XNormIn xn{Pin, Sin, (const uint16_t*)res_in, (uint16_t*)res_out, (const uint16_t*)gamma, eps};
+  if (xnm && !xn_ok(N, K, 1, R, xn)) return -1;
+  if (!xnm && (!X || !docqa_aligned16(X))) return -1;
+  if (epi == 1 ? (R % 16 || S != 1 || !Y) : !P) return -1;
+  const dim3 grid(N / R, S);
+  const uint16_t* x = (const uint16_t*)X;
+  const uint8_t* w = (const uint8_t*)Wq;
+  const uint8_t* e = (const uint8_t*)E;
+  int rc;
+  if (epi == 1)
+    rc = xnm ? launch_gemv4<EPI_GLU, true>(R, C, LB, KW, grid, s, x, w, e, (uint16_t*)Y, nullptr, N, K, Ks, xn)
+             : launch_gemv4<EPI_GLU, false>(R, C, LB, KW, grid, s, x, w, e, (uint16_t*)Y, nullptr, N, K, Ks, xn);
+  else
+    rc = xnm ? launch_gemv4<EPI_PARTIAL, true>(R, C, LB, KW, grid, s, x, w, e, nullptr, P, N, K, Ks, xn)
+             : launch_gemv4<EPI_PARTIAL, false>(R, C, LB, KW, grid, s, x, w, e, nullptr, P, N, K, Ks, xn);
+  if (rc) return rc;
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// Batch-1 LM head + greedy pick over MXFP4 weights: R (16 or 32) vocabulary rows per workgroup,
+// one (value, id) partial each, merged by argmax_merge_kernel.  ws_v / ws_i: N / R entries.
+int docqa_gemv4_argmax(const void* X, const void* Wq, const void* E, int64_t* out, float* outv, float* ws_v,
+                       int* ws_i, int N, int K, int R, int LB, int KW, int n_valid, hipStream_t s) {
+  int C = 0;
+  if (!gemv4_shape(N, K, 1, R, LB, KW, &C) || R % 16 || !X || !Wq || !E || !out || !ws_v || !ws_i ||
+      !docqa_aligned16(X) || !docqa_aligned16(Wq) || n_valid <= 0 || n_valid > N)
+    return -1;
+  const int rc = launch_gemv4<EPI_ARGMAX, false>(R, C, LB, KW, dim3(N / R), s, (const uint16_t*)X, (const uint8_t*)Wq,
+                                                 (const uint8_t*)E, nullptr, ws_v, N, K, K, XNormIn{}, ws_i, n_valid);
+  if (rc) return rc;
+  argmax_merge_kernel<<<1, 256, 0, s>>>(ws_v, ws_i, N / R, out, outv);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // FP8 weight stream for decode steps of 2..32 rows: dgemm_kernel's ring pipeline (256 threads,
 // workgroup = NT x 16 weight rows x all M rows x one K slice, X fragments straight to VGPRs
 // one k-block ahead, counted vmcnt waits, ring_barrier, XCD-aware slice remap,

@@ -143,8 +143,9 @@ def resolve_llama_config(name_or_path) -> LlamaConfig:
     return LlamaConfig.preset(str(name_or_path))
 
 
-# DOCQA_LLM_WEIGHTS values -> quantize to FP8
-LLM_WEIGHTS = {"bf16": False, "bfloat16": False, "fp8": True, "fp8-e4m3": True}
+# DOCQA_LLM_WEIGHTS values -> the LlamaModel method that quantizes to the streamed format
+LLM_WEIGHTS = {"bf16": None, "bfloat16": None, "fp8": "quantize_fp8", "fp8-e4m3": "quantize_fp8",
+               "mxfp4": "quantize_mxfp4", "fp4": "quantize_mxfp4"}
 
 
 def resolve_llama(name_or_path, device="cuda", seed: int = 0) -> LlamaModel:
@@ -153,9 +154,10 @@ def resolve_llama(name_or_path, device="cuda", seed: int = 0) -> LlamaModel:
     float32 for CPU rehearsals that compare TP = N against TP = 1 token for token (bf16
     rounds each TP split's sums differently, which flips near-tied greedy picks of a
     random-init model).
-    ``DOCQA_LLM_WEIGHTS`` (bf16 | fp8; default bf16): ``fp8`` quantizes the projections and the
-    LM head after loading (:meth:`LlamaModel.quantize_fp8`; TP = 1 only) -- on any dtype and
-    device, so a float32 / CPU model is the same quantized model on the reference path."""
+    ``DOCQA_LLM_WEIGHTS`` (bf16 | fp8 | mxfp4, alias fp4; default bf16): ``fp8`` / ``mxfp4``
+    quantize the projections and the LM head after loading (:meth:`LlamaModel.quantize_fp8` /
+    :meth:`LlamaModel.quantize_mxfp4`; TP = 1 only) -- on any dtype and device, so a float32 /
+    CPU model is the same quantized model on the reference path."""
     dtype = {"bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float32": torch.float32,
              "fp32": torch.float32}[os.environ.get("DOCQA_LLM_DTYPE", "bfloat16")]
     weights = os.environ.get("DOCQA_LLM_WEIGHTS", "bf16").lower()
@@ -166,7 +168,7 @@ def resolve_llama(name_or_path, device="cuda", seed: int = 0) -> LlamaModel:
     else:
         model = LlamaModel(LlamaConfig.preset(str(name_or_path)), device=device, dtype=dtype, seed=seed)
     if LLM_WEIGHTS[weights]:
-        model.quantize_fp8()
+        getattr(model, LLM_WEIGHTS[weights])()
     return model
 
 

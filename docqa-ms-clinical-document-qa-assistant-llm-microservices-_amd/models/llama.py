@@ -174,6 +174,9 @@ class LlamaModel:
         # FP8 weight copies (quantize_fp8): per layer {name: (q, s)} and the LM head's (q, s)
         self.fp8: list[dict] | None = None
         self.lm_head_fp8 = None
+        # MXFP4 weight copies (quantize_mxfp4): per layer {name: (q, e)} and the LM head's (q, e)
+        self.mx4: list[dict] | None = None
+        self.lm_head_mx4 = None
         if init:
             self._random_init(seed)
 
@@ -299,6 +302,8 @@ class LlamaModel:
         if self.tp != 1:
             raise ValueError("FP8 weights need tp_size == 1: per-row scales of the row-parallel O / down shards "
                              "would depend on the shard's K range and break the TP-invariant weights")
+        if self.mx4 is not None:
+            raise ValueError("quantize_mxfp4() was already applied: one model holds one streamed weight format")
         if self.fp8 is not None:
             return
         fp8 = []
@@ -314,9 +319,44 @@ class LlamaModel:
         self.lm_head_fp8 = (q, s)
         self.fp8 = fp8
 
+    def quantize_mxfp4(self) -> None:
+        """MXFP4 weight streaming for one-row decode steps (TP = 1; the GEMV, where its plan lists
+        the shape): every projection and the LM head get an OCP MXFP4 copy (q, e) -- e2m1 codes,
+        one e8m0 scale per 32 k (ops.quantize_mxfp4_rows) -- and the resident weights are REPLACED
+        by its exact image W' = code * 2^(e - 127).  Every kernel that reads W' (prefill, steps of
+        2+ rows, mixed steps, sampled logits, the CPU reference) then computes the same model the
+        4-bit kernel streams.  Lossier than FP8: a projection's output moves by roughly 11 % in
+        relative L2 norm for Gaussian weights -- an opt-in latency / quality trade.  The copies
+        cost memory (about +27 % of the projections) and save none.  Call after random init or
+        load_state_dict_hf, before any decode graph is captured."""
+        if self.tp != 1:
+            raise ValueError("MXFP4 weights need tp_size == 1: the block scales along K would survive a "
+                             "row-parallel split at multiples of 32, but the tensor-parallel path is neither "
+                             "built nor tested")
+        if self.fp8 is not None:
+            raise ValueError("quantize_fp8() was already applied: one model holds one streamed weight format")
+        if self.mx4 is not None:
+            return
+        mx4 = []
+        for L in self.layers:
+            d = {}
+            for k in self.FP8_WEIGHTS:
+                q, e = ops.quantize_mxfp4_rows(L[k])
+                L[k] = ops.dequantize_mxfp4_rows(q, e, self.dtype)
+                d[k] = (q, e)
+            mx4.append(d)
+        q, e = ops.quantize_mxfp4_rows(self.lm_head)
+        self.lm_head = ops.dequantize_mxfp4_rows(q, e, self.dtype)
+        self.lm_head_mx4 = (q, e)
+        self.mx4 = mx4
+        if self.device.type == "cuda":
+            # the quantizer's fp32 temporaries (gigabytes for the LM head) go back to the driver:
+            # the engine sizes the KV pool from the HBM that is free after the weights
+            torch.cuda.empty_cache()
+
     @property
     def weight_format(self) -> str:
-        return "fp8-e4m3" if self.fp8 is not None else "bf16"
+        return "fp8-e4m3" if self.fp8 is not None else "mxfp4" if self.mx4 is not None else "bf16"
 
     def weight_bytes(self) -> int:
         n = self.embed.numel() + self.lm_head.numel() + self.final_norm.numel()
@@ -326,6 +366,9 @@ class LlamaModel:
         if self.fp8 is not None:   # the FP8 copies are held next to the bf16 image
             for q, s in [self.lm_head_fp8] + [t for d in self.fp8 for t in d.values()]:
                 n += q.numel() * q.element_size() + s.numel() * s.element_size()
+        if self.mx4 is not None:   # the MXFP4 copies (codes + block scales), likewise
+            for q, e in [self.lm_head_mx4] + [t for d in self.mx4 for t in d.values()]:
+                n += q.numel() * q.element_size() + e.numel() * e.element_size()
         return n
 
     # ------------------------------------------------------------------ forward
@@ -361,6 +404,10 @@ class LlamaModel:
         # dgemm8_glu_ok); the rest, and every other step shape, run on the bf16 image W'
         use8 = (not meta.prefill and self.fp8 is not None and x.is_cuda
                 and 1 <= M <= ops.DGEMM8_MAX_ROWS)
+        # one-row decode steps of a quantize_mxfp4() model stream the MXFP4 copies the same way
+        # (ops.gemv4_plan / gemv4_glu_ok); a model holds one streamed format, w8 lists its projections
+        use4 = not meta.prefill and self.mx4 is not None and x.is_cuda and M == 1
+        wq = self.mx4 if use4 else self.fp8
         w8: dict = {}
         # a short prefill (<= ops.MID_M_MAX prompt tokens: batch-1 serving) has the decode
         # step's shape -- too few rows for the 256 x 256 prefill GEMM's tiles -- so it takes
@@ -387,6 +434,12 @@ class LlamaModel:
                     # one row, FP8 weights: the same GEMV over the (q, s) copy, half the bytes
                     w8[k] = (S8, R8)
                     plans[k] = (S8, lambda a, w, S=S8, R=R8: ops.gemv8_partial(a, w[0], w[1], S, R))
+                    continue
+                S4, R4 = ops.gemv4_plan(M, *L0[k].shape) if use4 else (0, 0)
+                if S4:
+                    # one row, MXFP4 weights: the GEMV over the (q, e) copy, 4.25 bits per weight
+                    w8[k] = (S4, R4)
+                    plans[k] = (S4, lambda a, w, S=S4, R=R4: ops.gemv4_partial(a, w[0], w[1], S, R))
                     continue
                 S8, t8 = ops.dgemm8_plan(M, *L0[k].shape) if use8 else (0, 64)
                 if S8:
@@ -420,6 +473,9 @@ class LlamaModel:
             if use8 and ops.gemv8_glu_ok(M, *L0["gate_up"].shape):
                 w8["gate_up"] = (1, 0)
                 glu = lambda a, w: ops.gemv8_glu(a, w[0], w[1])  # noqa: E731
+            elif use4 and ops.gemv4_glu_ok(M, *L0["gate_up"].shape):
+                w8["gate_up"] = (1, 0)
+                glu = lambda a, w: ops.gemv4_glu(a, w[0], w[1])  # noqa: E731
             elif use8 and ops.dgemm8_glu_ok(M, *L0["gate_up"].shape):
                 w8["gate_up"] = (1, 0)
                 glu = lambda a, w: ops.dgemm8_glu(a, w[0], w[1])  # noqa: E731
@@ -486,12 +542,15 @@ class LlamaModel:
         pd = None   # XN: the previous layer's down-projection slabs
         for i, L in enumerate(self.layers):
             kc, vc = kv_caches[i]
-            if w8:   # this layer's weights: the FP8 (q, s) pairs where the plan streams them
-                L = {**L, **{k: self.fp8[i][k] for k in w8}}
+            if w8:   # this layer's weights: the FP8 (q, s) / MXFP4 (q, e) pairs where the plan streams them
+                L = {**L, **{k: wq[i][k] for k in w8}}
             if sq:
                 if xn and pd is not None:
                     Sg, R = ops.gemv_plan(M, *self.layers[i]["qkv"].shape)
-                    if "qkv" in w8:
+                    if "qkv" in w8 and use4:
+                        qkv_slabs = ops.gemv4_partial_xn(pd, residual, res2, L["in_norm"], eps, *L["qkv"], sq,
+                                                         w8["qkv"][1])
+                    elif "qkv" in w8:
                         qkv_slabs = ops.gemv8_partial_xn(pd, residual, res2, L["in_norm"], eps, *L["qkv"], sq,
                                                          w8["qkv"][1])
                     elif Sg == sq:
@@ -584,7 +643,9 @@ class LlamaModel:
                                      meta.max_context, self.scale, meta.seq_order)
             nxt = self.layers[i + 1]["in_norm"] if i + 1 < nl else self.final_norm
             if xn:
-                if "gate_up" in w8:
+                if "gate_up" in w8 and use4:
+                    g = ops.gemv4_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, *L["gate_up"])
+                elif "gate_up" in w8:
                     g = ops.gemv8_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, *L["gate_up"])
                 elif ops.gemv_glu_ok(M, *L["gate_up"].shape):
                     g = ops.gemv_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, L["gate_up"])
@@ -697,7 +758,8 @@ class LlamaModel:
                                                    and ops.lm_head_argmax_shape_ok(N, K))
         if self.tp == 1:
             if fused:
-                return ops.lm_head_argmax(x, self.lm_head, self.cfg.vocab_size, fp8=self.lm_head_fp8)
+                return ops.lm_head_argmax(x, self.lm_head, self.cfg.vocab_size, fp8=self.lm_head_fp8,
+                                          mxfp4=self.lm_head_mx4)
             return self.greedy(ops.lm_head_logits(x, self.lm_head))
         if fused and self.vocab_valid > 0:
             ids, vals = ops.lm_head_argmax(x, self.lm_head, self.vocab_valid, with_values=True)

@@ -540,15 +540,22 @@ _LM_CFG = int(os.environ.get("DOCQA_LM_HEAD_CFG", "6"))
 _GEMV_LM = os.environ.get("DOCQA_GEMV_LM", "1") != "0"
 
 
-def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False, fp8=None):
+def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False, fp8=None, mxfp4=None):
     """Greedy token ids argmax(bf16(x @ w[:n_valid]^T)) with the LM-head GEMM and the argmax
     fused (mgemm.hip EPI_ARGMAX): the [M, vocab] logits never reach HBM.  ``with_values``:
     (ids, picked logit fp32) -- a vocab-parallel shard's candidates for comm.tp_argmax.
     ``fp8``: the (q, s) FP8 copy of ``w`` (:func:`quantize_fp8_rows`, ``w`` its exact image) --
     a one-row step then streams the codes (dgemm.hip gemv8_kernel EPI_ARGMAX), a 2..32-row
-    step too where :func:`dgemm8_argmax_ok` (dgemm8_kernel EPI_ARGMAX)."""
+    step too where :func:`dgemm8_argmax_ok` (dgemm8_kernel EPI_ARGMAX).
+    ``mxfp4``: the (q, e) MXFP4 copy of ``w`` (:func:`quantize_mxfp4_rows`, ``w`` its exact
+    image) -- a one-row step streams the codes where :func:`gemv4_argmax_ok` (gemv4_kernel
+    EPI_ARGMAX); every other step runs on ``w``."""
     if _gpu(x):
         N, K = w.shape
+        if mxfp4 is not None and n_valid > 0 and gemv4_argmax_ok(x.numel() // K, N, K):
+            R, lb, kw = _GEMV4_EPI[K]
+            ids, vals = _native().gemv4_argmax_val(x.contiguous(), mxfp4[0], mxfp4[1], int(n_valid), R, lb, kw)
+            return (ids, vals) if with_values else ids
         if fp8 is not None and n_valid > 0 and gemv8_argmax_ok(x.numel() // K, N, K):
             R, lb = _GEMV8_EPI[K]
             ids, vals = _native().gemv8_argmax_val(x.contiguous(), fp8[0], fp8[1], int(n_valid), R, lb)
@@ -798,6 +805,104 @@ def gemv8_glu_xn(Pin, res_in, res_out, gamma, eps: float, q, s, rows: int = 0, l
         return _native().gemv8_xn(Pin, res_in, res_out, gamma, float(eps), q, s, 1, int(rows) or R, int(lb) or l,
                                   True)
     return gemv_glu_xn(Pin, res_in, res_out, gamma, eps, dequantize_fp8_rows(q, s, res_in.dtype))
+
+
+# --------------------------------------------------------------------------- MXFP4 weights
+# Batch-1 GEMV over OCP MXFP4 weights (dgemm.hip gemv4_kernel): q [N, K / 2] pairs of e2m1 codes
+# and e [N, K / 32] e8m0 block scales, W' = code * 2^(e - 127) exactly the model's resident bf16
+# weights (LlamaModel.quantize_mxfp4), so a one-row step streams 4.25 bits per weight and
+# computes the same products as every other kernel does from W'.
+quantize_mxfp4_rows, dequantize_mxfp4_rows = ref.quantize_mxfp4_rows, ref.dequantize_mxfp4_rows
+
+_GEMV4 = os.environ.get("DOCQA_GEMV4", "1") != "0"
+# (N, K) -> (split-K count, weight rows per workgroup, codes per lane per load, waves along K) of
+# the split-K slab projections, and K -> (rows, codes per load, waves along K) of the SwiGLU /
+# LM-head argmax epilogues.  Every entry names an instantiation of gemv4_kernel (GEMV4_CASES) and
+# is listed only where benchmarks/bench_gemv_mxfp4.py measured its median below BOTH the bf16
+# GEMV's and the FP8 GEMV's shipped plans with disjoint min..max window ranges
+# (profiles/mxfp4_gemv_probe.log, us MXFP4 / FP8 / bf16: QKV 6144 x 4096 7.5 / 9.9 / 12.2, down
+# 4096 x 14336 9.7 / 13.3 / 20.2, gate|up 28672 x 4096 16.5 / 25.0 / 39.4, LM head 128256 x 4096
+# 48.5 / 89.5 / 159.0, 32768 x 4096 17.5 / 27.7 / 45.5; the test preset: gate|up 16384 x 2048 8.0 / 12.1 / 15.3, LM head 32000 x 2048 11.4 / 17.4 / 26.4).  The
+# slab table is keyed by the whole shape because the narrow, latency-bound projections LOST at the
+# same K and keep the bf16 GEMV on W': O 4096 x 4096 (6.1 us against FP8's 6.2, ranges overlap),
+# and the test preset's QKV 3072 x 2048 (6.2 / 6.4 / 6.8, overlapping), O 2048 x 2048 (5.1 -
+# 5.3 against bf16's 4.8) and down 2048 x 8192 (5.2 / 6.0 / 7.9 in the first run of the log, but
+# 6.05 against FP8's 6.4 with overlapping ranges in the second).
+_GEMV4_PLAN = {(6144, 4096): (1, 8, 32, 2), (4096, 14336): (1, 4, 16, 2)}
+_GEMV4_EPI = {2048: (16, 32, 1), 4096: (16, 32, 2)}
+# (rows, chunks per lane, codes per load, waves along K) instantiated for slabs -- the smallest K
+# an entry takes is chunks x 64 x codes x waves; XN: also with the in-kernel input row
+# (K <= 4096); EPI: the SwiGLU / argmax epilogues
+GEMV4_CASES = [(16, 1, 32, 1), (32, 1, 32, 1), (8, 1, 32, 2), (16, 1, 32, 2), (16, 2, 32, 1), (8, 1, 16, 4),
+               (8, 1, 16, 2), (8, 1, 32, 4), (16, 1, 32, 4), (4, 7, 32, 1), (8, 7, 32, 1), (4, 7, 16, 2)]
+GEMV4_XN_CASES = GEMV4_CASES[:7]
+GEMV4_EPI_CASES = [(16, 1, 32, 1), (32, 1, 32, 1), (16, 1, 32, 2), (32, 1, 32, 2), (16, 2, 32, 1), (16, 1, 16, 4)]
+
+
+def gemv4_plan(M: int, N: int, K: int) -> tuple[int, int]:
+    """(split-K count, weight rows per workgroup) of the MXFP4-weight GEMV for a one-row
+    projection; (0, 0) where the kernel has no instantiation or did not beat the bf16 and FP8
+    GEMVs (the caller then streams the bf16 image W').  DOCQA_GEMV4=0 disables."""
+    S, R, lb, kw = _GEMV4_PLAN.get((N, K), (0, 0, 0, 0))
+    if not _GEMV4 or M != 1 or not S or N % R or (K // S) % (64 * lb * kw):
+        return 0, 0
+    if (R, K // S // (64 * lb * kw), lb, kw) not in GEMV4_CASES:
+        return 0, 0
+    return S, R
+
+
+def gemv4_cfg(N: int, K: int, splits: int = 1) -> tuple[int, int]:
+    """(codes per lane per load, waves along K) the plan table uses for this shape; where it lists
+    none, whole-block loads with as many waves along K as leave one chunk per lane."""
+    if (N, K) in _GEMV4_PLAN and _GEMV4_PLAN[(N, K)][0] == splits:
+        return _GEMV4_PLAN[(N, K)][2:]
+    ks = K // max(splits, 1)
+    return 32, next((w for w in (4, 2, 1) if ks % (2048 * w) == 0), 1)
+
+
+def gemv4_glu_ok(M: int, N: int, K: int) -> bool:
+    """The batch-1 gate|up projection with SwiGLU on the MXFP4-weight GEMV."""
+    R, lb, kw = _GEMV4_EPI.get(K, (0, 0, 0))
+    return bool(_GEMV4 and M == 1 and R and N % R == 0 and K % (64 * lb * kw) == 0
+                and (R, K // (64 * lb * kw), lb, kw) in GEMV4_EPI_CASES)
+
+
+def gemv4_argmax_ok(M: int, N: int, K: int) -> bool:
+    """The batch-1 LM head + greedy pick on the MXFP4-weight GEMV."""
+    return gemv4_glu_ok(M, N, K)
+
+
+def gemv4_partial(x, q, e, splits: int, rows: int, lb: int = 0, kw: int = 0):
+    """fp32 slabs [S, 1, N] of one row x @ W'^T on the MXFP4-weight GEMV (:func:`gemv4_plan`)."""
+    if _gpu(x):
+        l, k = (int(lb), int(kw)) if lb and kw else gemv4_cfg(q.shape[0], q.shape[1] * 2, splits)
+        return _native().gemv4(x.contiguous(), q, e, int(splits), int(rows), l, k, False)
+    return gemv_partial(x, dequantize_mxfp4_rows(q, e, x.dtype), splits, rows)
+
+
+def gemv4_partial_xn(Pin, res_in, res_out, gamma, eps: float, q, e, splits: int, rows: int, lb: int = 0,
+                     kw: int = 0):
+    """:func:`gemv_partial_xn` (input row built in-kernel) over MXFP4 weights."""
+    if _gpu(Pin):
+        l, k = (int(lb), int(kw)) if lb and kw else gemv4_cfg(q.shape[0], q.shape[1] * 2, splits)
+        return _native().gemv4_xn(Pin, res_in, res_out, gamma, float(eps), q, e, int(splits), int(rows), l, k, False)
+    return gemv_partial_xn(Pin, res_in, res_out, gamma, eps, dequantize_mxfp4_rows(q, e, res_in.dtype), splits, rows)
+
+
+def gemv4_glu(x, q, e, rows: int = 0, lb: int = 0, kw: int = 0):
+    """silu(x Wg^T) * (x Wu^T) for one row over MXFP4 8-interleaved gate|up weights."""
+    if _gpu(x):
+        R, l, k = (int(rows), int(lb), int(kw)) if rows and lb and kw else _GEMV4_EPI.get(q.shape[1] * 2, (16, 32, 1))
+        return _native().gemv4(x.contiguous(), q, e, 1, R, l, k, True)
+    return gemv_glu(x, dequantize_mxfp4_rows(q, e, x.dtype))
+
+
+def gemv4_glu_xn(Pin, res_in, res_out, gamma, eps: float, q, e, rows: int = 0, lb: int = 0, kw: int = 0):
+    """:func:`gemv_glu_xn` (input row built in-kernel, SwiGLU epilogue) over MXFP4 weights."""
+    if _gpu(Pin):
+        R, l, k = (int(rows), int(lb), int(kw)) if rows and lb and kw else _GEMV4_EPI.get(q.shape[1] * 2, (16, 32, 1))
+        return _native().gemv4_xn(Pin, res_in, res_out, gamma, float(eps), q, e, 1, R, l, k, True)
+    return gemv_glu_xn(Pin, res_in, res_out, gamma, eps, dequantize_mxfp4_rows(q, e, res_in.dtype))
 
 
 # 2..DGEMM8_MAX_ROWS-row decode steps over the same (q, s) copies (dgemm.hip dgemm8_kernel: the

@@ -181,6 +181,55 @@ def dequantize_fp8_rows(q, s, dtype=torch.bfloat16):
     return (q.float() * s.float()[:, None]).to(dtype)
 
 
+MXFP4_BLOCK = 32         # k per OCP e8m0 block scale
+# magnitudes of the OCP e2m1 codes 0..7 (bit 3 of a code is the sign)
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# amax / scale lands in (3.5, 7]: 7 is the rounding boundary above the top code 6 (everything up
+# to it rounds to 6 anyway), so a non-zero block's top code is 4 or 6 and quantizing the image
+# again gives the same (q, e) -- the 464 of the FP8 rule above
+_MXFP4_MIN_EXP, _MXFP4_MAX_EXP = -126, 125
+
+
+def quantize_mxfp4_rows(w):
+    """OCP MXFP4 weight format: ``w`` [N, K], K % 32 == 0 -> (q [N, K / 2] uint8, e [N, K / 32]
+    uint8).  ``q`` holds two e2m1 codes per byte, element 2j in bits 0..3 and 2j + 1 in bits 4..7
+    (the torch.float4_e2m1fn_x2 order); ``e`` one e8m0 scale 2^(e - 127) per block of 32
+    consecutive k, ``2^ceil(log2(amax / 7))`` with the exponent clamped to [-126, 125] (e = 127 for
+    an all-zero block; 255 = NaN is never produced).  Elements round to the nearest code, ties to
+    the even code, saturating at +-6; NaN -> 0, +-inf saturates.  ``code * scale`` has a 1-bit
+    mantissa, so the image is exact in bf16 (:func:`dequantize_mxfp4_rows`)."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"MXFP4 rows need K % {MXFP4_BLOCK} == 0 (got K = {K})")
+    wf = torch.nan_to_num(w.detach().float(), nan=0.0, posinf=3e38, neginf=-3e38).clamp_(-3e38, 3e38)
+    wb = wf.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wb.abs().amax(dim=2)
+    # amax = m * 2^ex, m in [0.5, 1); 7 = 0.875 * 2^3 -- compared exactly, no division
+    m, ex = torch.frexp(amax)
+    p = torch.where(m > 0.875, ex - 2, ex - 3).clamp_(_MXFP4_MIN_EXP, _MXFP4_MAX_EXP)
+    p = torch.where(amax > 0, p, torch.zeros_like(p))
+    v = torch.ldexp(wb, -p[:, :, None])                     # exact: a power of two
+    a = v.abs().clamp_(max=6.0)
+    # code index of the nearest magnitude; torch.round is half-to-even, which on each of the three
+    # uniform stretches (step 0.5 below 2, 1 below 4, 2 above) is ties-to-even-code
+    idx = torch.where(a < 2, torch.round(a * 2), torch.where(a < 4, torch.round(a) + 2, torch.round(a / 2) + 4))
+    idx = idx.to(torch.uint8)
+    code = idx | (((v < 0) & (idx > 0)).to(torch.uint8) << 3)     # no negative zero
+    code = code.view(N, K // 2, 2)
+    q = code[:, :, 0] | (code[:, :, 1] << 4)
+    return q.contiguous(), (p + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4_rows(q, e, dtype=torch.bfloat16):
+    """The image ``code * 2^(e - 127)`` [N, K] of :func:`quantize_mxfp4_rows` in ``dtype`` (exact in
+    bf16 and fp32)."""
+    N, K = q.shape[0], q.shape[1] * 2
+    lut = torch.tensor(_E2M1 + tuple(-x for x in _E2M1), dtype=torch.float32, device=q.device)
+    codes = torch.stack([q & 0xF, q >> 4], dim=2).view(N, K).int()
+    vals = lut[codes].view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    return torch.ldexp(vals, e.to(torch.int32)[:, :, None] - 127).view(N, K).to(dtype)
+
+
 def bias_act(x, bias, residual, gelu):
     y = x.float()
     if residual is not None:

@@ -201,9 +201,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--tiny", action="store_true", help="tiny random models (CPU demo / CI)")
     ap.add_argument("--llm", default="llama3-8b")
-    ap.add_argument("--llm-weights", choices=("bf16", "fp8"), default=None,
+    ap.add_argument("--llm-weights", choices=("bf16", "fp8", "mxfp4"), default=None,
                     help="generator weight format (DOCQA_LLM_WEIGHTS): fp8 streams per-row e4m3 weights in "
-                         "decode steps of up to 32 rows where measured faster (TP = 1)")
+                         "decode steps of up to 32 rows where measured faster (TP = 1); mxfp4 streams OCP 4-bit "
+                         "block-scaled weights in one-row decode steps (TP = 1; lossier than fp8)")
     ap.add_argument("--kv-cache", choices=("bf16", "fp8"), default=None,
                     help="paged KV cache format (DOCQA_KV_CACHE): fp8 stores K/V as e4m3 codes -- half the "
                          "bytes per block, twice the blocks for one DOCQA_KV_MEM_FRACTION")

@@ -246,8 +246,8 @@ def register(app: FastAPI, settings, metrics) -> None:
                            "size": int(m.weight_bytes()), "digest": "",
                            "details": {"format": "safetensors", "family": "llama", "families": ["llama"],
                                        "parameter_size": f"{m.cfg.num_params() / 1e9:.1f}B",
-                                       "quantization_level": ("F8_E4M3" if getattr(m, "weight_format", "bf16")
-                                                              == "fp8-e4m3" else "BF16"),
+                                       "quantization_level": {"fp8-e4m3": "F8_E4M3", "mxfp4": "MXFP4"}.get(
+                                           getattr(m, "weight_format", "bf16"), "BF16"),
                                        # the paged KV format (DOCQA_KV_CACHE); not an Ollama field
                                        "kv_cache_type": ("fp8_e4m3" if getattr(pipe.engine, "kv_fp8", False)
                                                          else "bf16")}})
