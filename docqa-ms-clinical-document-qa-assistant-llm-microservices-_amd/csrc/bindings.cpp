@@ -1202,6 +1202,55 @@ std::tuple<at::Tensor, at::Tensor> dgemm8_argmax_val(const at::Tensor& x, const 
   return {out, outv};
 }
 
+// 2..32-row decode projections over MXFP4 weights (dgemm.hip dgemm4_kernel); a shape without an
+// instantiation launches nothing and raises, naming the op
+static int dgemm4_rows(const at::Tensor& x, const at::Tensor& q, const at::Tensor& e, const char* op, int* K) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(), op,
+              ": x must be a contiguous bfloat16 GPU tensor");
+  *K = check_mx4w(q, e, op);
+  TORCH_CHECK(x.size(-1) == *K, op, ": K mismatch");
+  const int64_t M = x.numel() / *K;
+  TORCH_CHECK(M <= 32, op, ": at most 32 rows, got ", M);
+  return (int)M;
+}
+
+at::Tensor dgemm4_partial(const at::Tensor& x, const at::Tensor& q, const at::Tensor& e, int64_t splits,
+                          int64_t tile_rows) {
+  int K = 0;
+  const int M = dgemm4_rows(x, q, e, "dgemm4_partial", &K), N = q.size(0);
+  TORCH_CHECK(splits >= 1, "dgemm4_partial: splits >= 1");
+  c10::DeviceGuard g(x.device());
+  auto part = at::empty({splits, M, N}, x.options().dtype(at::kFloat));
+  CHECK_RC(docqa_dgemm4_partial(x.data_ptr(), q.data_ptr(), e.data_ptr(), part.data_ptr<float>(), M, N, K,
+                                (int)splits, (int)tile_rows, stream()), "dgemm4_partial");
+  return part;
+}
+
+at::Tensor dgemm4_glu(const at::Tensor& x, const at::Tensor& q, const at::Tensor& e) {
+  int K = 0;
+  const int M = dgemm4_rows(x, q, e, "dgemm4_glu", &K), N = q.size(0);
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({M, N / 2}, x.options());
+  CHECK_RC(docqa_dgemm4_glu(x.data_ptr(), q.data_ptr(), e.data_ptr(), out.data_ptr(), M, N, K, stream()),
+           "dgemm4_glu");
+  return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> dgemm4_argmax_val(const at::Tensor& x, const at::Tensor& q, const at::Tensor& e,
+                                                     int64_t n_valid) {
+  int K = 0;
+  const int M = dgemm4_rows(x, q, e, "dgemm4_argmax_val", &K), N = q.size(0);
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({M}, x.options().dtype(at::kLong));
+  auto outv = at::empty({M}, x.options().dtype(at::kFloat));
+  auto ws_v = at::empty({M, N / 64 + 1}, x.options().dtype(at::kFloat));
+  auto ws_i = at::empty({M, N / 64 + 1}, x.options().dtype(at::kInt));
+  CHECK_RC(docqa_dgemm4_argmax(x.data_ptr(), q.data_ptr(), e.data_ptr(), out.data_ptr<int64_t>(),
+                               outv.data_ptr<float>(), ws_v.data_ptr<float>(), ws_i.data_ptr<int>(), M, N, K,
+                               (int)n_valid, stream()), "dgemm4_argmax_val");
+  return {out, outv};
+}
+
 at::Tensor dgemm(const at::Tensor& x, const at::Tensor& w, int64_t splits) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
   const int K = x.size(-1), N = w.size(0);
@@ -1752,6 +1801,9 @@ TORCH_LIBRARY(docqa, m) {
   m.def("dgemm8_partial(Tensor x, Tensor q, Tensor scale, int splits, int tile_rows=64) -> Tensor");
   m.def("dgemm8_glu(Tensor x, Tensor q, Tensor scale) -> Tensor");
   m.def("dgemm8_argmax_val(Tensor x, Tensor q, Tensor scale, int n_valid) -> (Tensor, Tensor)");
+  m.def("dgemm4_partial(Tensor x, Tensor q, Tensor e, int splits, int tile_rows=64) -> Tensor");
+  m.def("dgemm4_glu(Tensor x, Tensor q, Tensor e) -> Tensor");
+  m.def("dgemm4_argmax_val(Tensor x, Tensor q, Tensor e, int n_valid) -> (Tensor, Tensor)");
   m.def("pgemm(Tensor x, Tensor w, int epi=0) -> Tensor");
   m.def("pgemm_partial(Tensor x, Tensor w, int splits) -> Tensor");
   m.def("mgemm_argmax_val(Tensor x, Tensor w, int n_valid, int cfg=0) -> (Tensor, Tensor)");
@@ -1852,6 +1904,9 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("dgemm8_partial", &dgemm8_partial);
   m.impl("dgemm8_glu", &dgemm8_glu);
   m.impl("dgemm8_argmax_val", &dgemm8_argmax_val);
+  m.impl("dgemm4_partial", &dgemm4_partial);
+  m.impl("dgemm4_glu", &dgemm4_glu);
+  m.impl("dgemm4_argmax_val", &dgemm4_argmax_val);
   m.impl("paged_decode_fused", &paged_decode_fused);
   m.impl("paged_decode_cascade", &paged_decode_cascade);
   m.impl("paged_decode_cascade_rope", &paged_decode_cascade_rope);

@@ -205,6 +205,15 @@ int docqa_dgemm8_partial(const void* X, const void* Wq, const float* scale, floa
 int docqa_dgemm8_glu(const void* X, const void* Wq, const float* scale, void* Y, int M, int N, int K, hipStream_t s);
 int docqa_dgemm8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
                         int* ws_i, int M, int N, int K, int n_valid, hipStream_t s);
+// 2..32-row decode projections over MXFP4 weights (dgemm.hip dgemm4_kernel: the same ring over
+// Wq [N, K / 2] e2m1 code pairs and E [N, K / 32] e8m0 block scales, K slices of whole 2048-deep
+// ring turns): outputs as docqa_dgemm8_*; slab tiles of 64, 32 or 16 weight rows (tile_rows).  -1
+// (nothing launched) for a shape without an instantiation.
+int docqa_dgemm4_partial(const void* X, const void* Wq, const void* E, float* P, int M, int N, int K, int S,
+                         int tile_rows, hipStream_t s);
+int docqa_dgemm4_glu(const void* X, const void* Wq, const void* E, void* Y, int M, int N, int K, hipStream_t s);
+int docqa_dgemm4_argmax(const void* X, const void* Wq, const void* E, int64_t* out, float* outv, float* ws_v,
+                        int* ws_i, int M, int N, int K, int n_valid, hipStream_t s);
 int docqa_embed_rmsnorm(const int* ids, const void* table, const void* w, void* h, void* x, int T, int H, int V,
                         float eps, hipStream_t s);
 int docqa_fp32_gemm_nt(const float* x, int nq, int d, const float* w, int n, float* out, hipStream_t s);

@@ -1676,3 +1676,355 @@ int docqa_dgemm8_argmax(const void* X, const void* Wq, const float* scale, int64
   DOCQA_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------
+// MXFP4 weight stream for decode steps of 2..32 rows: dgemm8_kernel's ring pipeline (256 threads,
+// workgroup = NT x 16 weight rows x all M rows x one K slice, X fragments straight to VGPRs two
+// stages ahead, counted vmcnt waits, ring_barrier, XCD-aware slice remap,
+// v_mfma_f32_16x16x32_bf16) over the (Wq, E) copies of gemv4_kernel: Wq [N, K / 2] bytes of two
+// e2m1 codes (element 2j in bits 0..3), E [N, K / 32] e8m0 block scales.
+//   * Ring depth: a stage keeps the bf16 / FP8 stage's BYTES -- 256 B per weight row, now 512
+//     codes = 16 scale blocks -- in 4 slots, so the NT LDS-DMA wave-instructions (glds16<true>,
+//     16 B per lane, nt) per wave per stage, the issue order and the counted waits carry over.
+//     K granule: one ring turn = 4 x 512 = 2048 (Ks % 2048 == 0: 4096 is 2 turns, 14336 is 7).
+//     The 128-B-per-row stage (granule 1024) was not built.  What the narrow projections lack
+//     at this granule is workgroups (O 4096 x 4096: 64 tiles x 2 slices for 256 CUs), and fewer
+//     n-tiles per workgroup give them without touching the stage: NT = 2 | 1 (32 | 16 weight
+//     rows, a 32 | 16 KB ring, more workgroups per CU) for the slab epilogue -- O at 8 rows 6.7 us
+//     at NT = 2, S = 2 against 8.5 at NT = 4 (profiles/mxfp4_dgemm_probe.log).  X is re-read per
+//     workgroup, so the wide projections keep NT = 4 | 7.
+//   * LDS layout: stage = [NT 16][256 B], 16 chunks of 16 B per row, byte for byte the FP8 stage
+//     with the same source swizzle: chunk c of row r lands at chunk position c ^ (r & 15).  A
+//     chunk is exactly one scale block (32 codes).
+//   * B fragment: the k order inside an MFMA is free as long as A and B agree, so lane (fr =
+//     lane & 15, fq = lane >> 4) owns a WHOLE block: block c = 4 g + fq of its wave's 4 G blocks
+//     of the stage (G = 1 at MT = 1, 2 at MT = 2), row 16 nt + fr -- one ds_read_b128 at
+//       row * 256 + ((c ^ fr) << 4)
+//     and one scale byte feed the lane's B operand of four MFMAs (dword t = codes 8 t .. 8 t + 7
+//     for MFMA t).  The matching A operands are the 64 contiguous bytes X[row][32 c + 8 t ..]:
+//     MFMA t of group g contracts k = 32 (4 g + fq) + 8 t + e over (fq, e), the four of them all
+//     128 k of the group.
+//     ds_read_b128 is served in four 16-lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and
+//     the same + 32, bank = (addr / 4) % 64 (MI355X_MICROARCH.md, LDS): a group is conflict-free
+//     iff its 16 lanes hit 16 distinct 16-B slots of the 256-B bank row.  row * 256 == 0 (mod
+//     256), so the slot is c ^ fr.  The first group holds fq = 0 with fr in {0-3, 12-15} and
+//     fq = 1 with fr in {4-11}; with c0 the (even) block of fq = 0 its slots are c0 ^ {0-3, 12-15}
+//     and (c0 ^ 1) ^ {4-11} = c0 ^ {4-11} (x ^ 1 maps {4-11} onto itself): all 16.  The second
+//     group swaps the two fr sets, the upper two have fq = 2 | 3 (x ^ 2 and x ^ 3 map both sets
+//     onto themselves): every group is conflict-free.
+//   * Widening: v_cvt_scalef32_pk_bf16_fp4 (two codes per instruction, four per 8-code fragment)
+//     with the block scale as its fp32 operand E << 23 -- exact (a code times a power of two is
+//     a bf16 value), so the fp32 accumulators need no scaling afterwards.  No scaled MFMA: it
+//     would need quantized activations, i.e. another model.
+//   * Block scales: per-lane global loads into VGPRs, not one more LDS-DMA piece.  A lane needs
+//     one byte per n-tile per group; the four fq lanes' bytes are one aligned dword (G = 2: two
+//     dwords 4 B apart, one dwordx2), so each lane loads that word (the 4 fq lanes coalesce) and
+//     picks byte fq with a shift and a mask.  That is NT loads per stage, issued FIRST in the stage's X
+//     set and therefore retired by the wait that retires the stage's X fragments; a DMA piece of
+//     NT x 256 B is not a whole number of 1-KB wave-instructions at NT = 7, would be issued by
+//     some waves only (unequal vmcnt counts per wave) and costs a ds_read per n-tile.
+//   * vmcnt: the per-stage vector-memory set of a lane is XV = NT scale loads + SPW X fragments
+//     (SPW = 4 G), issued as one group "X(j)".  Issue order W0 X0 W1 X1 W2 | step i: X(i+2)
+//     W(i+3); the ops issued after X(i) are W(i+1) X(i+1) W(i+2), so vmcnt(2 NT + XV) retires
+//     X(i) and, issued before it, W(i).  At most 2 NT + XV + NT + XV <= 51 in flight (NT = 7,
+//     MT = 2), inside the 6-bit counter.
+//   * MT = 1 (2..16 rows: four waves split the stage's 16 blocks, 4 each) and MT = 2 (17..32
+//     rows: two k-groups of 8 blocks).  33+ rows stay on W', as in dgemm8_kernel: every wave
+//     would widen every fragment and the bf16 kernel is no longer bound by weight bytes alone.
+//   * Where the time goes: a stage holds twice the FP8 stage's k, so twice its conversions, MFMAs
+//     and X bytes per weight byte.  The kernel is bound by that per-k work, not by HBM: 3.2-4.0
+//     TB/s of codes and scales at 2 rows (FP8: 4.4-5.7), and the time grows with the rows (LM
+//     head 70 / 84 / 107 / 145 us at 2 / 8 / 16 / 32 rows) as the X fragments stop hitting the
+//     same cache lines.  It beats W' by 2.2-2.7 x on the wide projections at 2..8 rows and still
+//     by 1.3-1.6 x at 32; against FP8 it wins up to 8 rows and loses from 16.
+//   * Epilogues: EPI_PARTIAL / EPI_GLU / EPI_ARGMAX exactly as dgemm8_kernel.
+namespace {
+constexpr int BK4 = 512;                  // codes per weight row per stage (256 B)
+constexpr int BKB4 = BK4 / 2;             // ... bytes
+
+__device__ __forceinline__ void gload_u32(uint32_t& d, const void* p) {
+  asm volatile("global_load_dword %0, %1, off" : "=v"(d) : "v"(p) : "memory");
+}
+__device__ __forceinline__ void gload_u32(u32x2& d, const void* p) {
+  asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(d) : "v"(p) : "memory");
+}
+__device__ __forceinline__ uint32_t word_of(uint32_t v, int) { return v; }
+__device__ __forceinline__ uint32_t word_of(u32x2 v, int g) { return v[g]; }
+
+// 8 e2m1 codes (one dword) times the block scale -> the bf16x8 B fragment
+__device__ __forceinline__ bf16x8 widen4(uint32_t c, float scale) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 0);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 1);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 2);
+  const bf16x2 e = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, scale, 3);
+  return bf16x8{a[0], a[1], b[0], b[1], d[0], d[1], e[0], e[1]};
+}
+
+template <int EPI, int MT, int NT>
+__global__ __launch_bounds__(256) void dgemm4_kernel(const uint16_t* __restrict__ X, const uint8_t* __restrict__ W,
+                                                     const uint8_t* __restrict__ E, uint16_t* __restrict__ Y,
+                                                     float* __restrict__ P, int M, int N, int K, int Ks,
+                                                     int xcd_remap, float* __restrict__ pv = nullptr,
+                                                     int* __restrict__ pi = nullptr, int n_valid = 0) {
+  static_assert(MT == 1 || MT == 2, "2..16 rows (MT = 1) or 17..32 rows (MT = 2)");
+  static_assert(EPI == EPI_PARTIAL || EPI == EPI_GLU || EPI == EPI_ARGMAX, "slabs, SwiGLU or argmax");
+  constexpr int NSR = NS;                        // ring slots
+  constexpr int KW = 4 / MT;                     // k-groups
+  constexpr int G = 4 / KW;                      // 4-block groups per wave per stage
+  constexpr int SPW = 4 * G;                     // k-steps (= X fragments) per wave per stage
+  constexpr int XV = NT + SPW;                   // scale words + X fragments per stage
+  constexpr int VW = 2 * NT + XV;                // vector-memory ops in flight at the top of a step
+  constexpr int STAGE = NT * 16 * BKB4;          // bytes of one W stage (NT x 4 KB)
+  static_assert(3 * NT + 2 * XV <= 63, "loads in flight per lane must fit the vmcnt counter");
+  typedef std::conditional_t<G == 1, uint32_t, u32x2> ST;   // a lane's scale bytes of one stage and n-tile
+  __shared__ __attribute__((aligned(16))) uint8_t sw[NSR * STAGE];   // W ring
+  int tile = blockIdx.x, slice = blockIdx.y;
+  if (xcd_remap) {   // XCD x only runs slice x % S (see dgemm_kernel)
+    const int S = gridDim.y;
+    const int L = blockIdx.x + blockIdx.y * gridDim.x;
+    const int xcd = L & 7, j = L >> 3;
+    slice = xcd % S;
+    tile = j * (8 / S) + xcd / S;
+  }
+  const int n0 = tile * NT * 16;
+  const int kbeg = slice * Ks;
+  const int nkb = Ks / BK4;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const int mt = wave % MT, kg = wave / MT;
+  // this lane's 64 X bytes per group: k = 128 (G kg + g) + 32 fq + 8 t of the stage
+  const uint16_t* xrow = X + (size_t)min(mt * 16 + fr, M - 1) * K + kbeg + kg * SPW * 32 + fq * 32;
+  // ... and its scale word: blocks 4 (G kg + g) .. + 3 of the stage, row 16 nt + fr
+  const uint8_t* erow = E + (size_t)(n0 + fr) * (K >> 5) + (kbeg >> 5) + kg * SPW;
+  const uint32_t ring = lds_u32(sw);
+
+  f32x4 acc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // W stage j -> ring slot j % NSR: 4 NT wave-instructions of 64 lanes x 16 B (4 rows each), NT
+  // per wave, source XOR-swizzled; clamped past the last stage (see dgemm_kernel)
+  const uint8_t* wsrc[NT];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int p = (i * 4 + wave) * 64 + lane;
+    const int r = p >> 4;
+    wsrc[i] = W + (size_t)(n0 + r) * (K >> 1) + (kbeg >> 1) + (((p & 15) ^ (r & 15)) << 4);
+  }
+  auto stage_w = [&](int j) {
+    const int koff = min(j, nkb - 1) * BKB4;
+    const uint32_t dst = ring + (uint32_t)((j % NSR) * STAGE);
+#pragma unroll
+    for (int i = 0; i < NT; ++i) glds16<true>(wsrc[i] + koff, dst + (uint32_t)((i * 4 + wave) * 1024));
+  };
+  // X(j): the stage's scale words first, then its X fragments
+  auto load_x = [&](ST (&sc)[NT], bf16x8 (&x)[SPW], int j) {
+    const int jj = min(j, nkb - 1);
+    const uint8_t* es = erow + jj * (BK4 / 32);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) gload_u32(sc[nt], es + (size_t)nt * 16 * (K >> 5));
+    const uint16_t* src = xrow + jj * BK4;
+    gload16<0>(x[0], src);
+    gload16<16>(x[1], src);
+    gload16<32>(x[2], src);
+    gload16<48>(x[3], src);
+    if constexpr (G == 2) {
+      gload16<256>(x[4], src);
+      gload16<272>(x[5], src);
+      gload16<288>(x[6], src);
+      gload16<304>(x[7], src);
+    }
+  };
+  auto name_sc = [&](ST (&sc)[NT]) {   // retired by the wait just before: see dgemm8_kernel
+#pragma unroll
+    for (int i = 0; i < NT; ++i) asm volatile("" : "+v"(sc[i]));
+  };
+  auto mma = [&](const ST (&sc)[NT], const bf16x8 (&x)[SPW], int j) {
+    const uint8_t* src = sw + (j % NSR) * STAGE + fr * BKB4;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const int c = (kg * G + g) * 4 + fq;
+      const int off = (c ^ fr) << 4;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const u32x4 cw = *reinterpret_cast<const u32x4*>(src + nt * 16 * BKB4 + off);
+        // e8m0 byte fq of the word -> fp32 2^(e - 127)
+        const float scale = __uint_as_float(((word_of(sc[nt], g) >> (fq * 8)) & 0xffu) << 23);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[g * 4 + t], widen4(cw[t], scale), acc[nt], 0, 0, 0);
+      }
+    }
+  };
+  bf16x8 x0[SPW], x1[SPW], x2[SPW], x3[SPW];
+  ST s0[NT], s1[NT], s2[NT], s3[NT];
+#define RING_STEP4(I, SC, XC, SNX, XNX)                                                 \
+  wait_vm_n<VW>(XC);                                                                    \
+  name_sc(SC);                                                                          \
+  ring_barrier();                                                                       \
+  load_x(SNX, XNX, (I) + 2);                                                            \
+  stage_w((I) + NSR - 1);                                                               \
+  mma(SC, XC, I);
+  stage_w(0);
+  load_x(s0, x0, 0);
+  stage_w(1);
+  load_x(s1, x1, 1);
+  stage_w(2);
+  for (int i = 0; i < nkb; i += 4) {
+    RING_STEP4(i, s0, x0, s2, x2)
+    RING_STEP4(i + 1, s1, x1, s3, x3)
+    RING_STEP4(i + 2, s2, x2, s0, x0)
+    RING_STEP4(i + 3, s3, x3, s1, x1)
+  }
+#undef RING_STEP4
+  // drain the clamped tail loads; naming every buffer keeps its registers reserved until then
+  wait_vm_n<0>(x0);
+  keep_live(x1);
+  keep_live(x2);
+  keep_live(x3);
+  name_sc(s0);
+  name_sc(s1);
+  name_sc(s2);
+  name_sc(s3);
+
+  // sum the KW k-groups through LDS (ring is free after the last barrier + wait)
+  __syncthreads();
+  f32x4* red = reinterpret_cast<f32x4*>(sw);        // [wave][nt][lane] = one slot
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) red[(wave * NT + nt) * 64 + lane] = acc[nt];
+  __syncthreads();
+  const float* rf = reinterpret_cast<const float*>(sw);
+  auto sum_k = [&](int m, int nt, int ln, int r) {
+    float v = 0.f;
+#pragma unroll
+    for (int g = 0; g < KW; ++g) v += rf[(((g * MT + m) * NT + nt) * 64 + ln) * 4 + r];
+    return v;
+  };
+  // C/D map of 16x16x32: col = lane & 15 (weight row), row = 4 * (lane >> 4) + r (X row)
+  if constexpr (EPI == EPI_ARGMAX) {
+    // the [rows, NT 16] logit tile through LDS (past the k-group reduction area), 4 lanes per
+    // row -> one (value, id) partial per (row, tile)
+    constexpr int TP = NT * 16 + 1;
+    float* tl = reinterpret_cast<float*>(sw) + 4 * NT * 64 * 4;
+    for (int idx = tid; idx < MT * NT * 256; idx += 256) {
+      const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
+      const int nt = q % NT, m = q / NT;
+      tl[(m * 16 + (ln >> 4) * 4 + r) * TP + nt * 16 + (ln & 15)] = sum_k(m, nt, ln, r);
+    }
+    __syncthreads();
+    const int ntiles = N / (NT * 16);
+    for (int rr = tid >> 2; rr < MT * 16; rr += 64) {
+      float bv = -FLT_MAX;
+      int bi = 0x7fffffff;
+      const int c0 = (tid & 3) * (NT * 4);
+#pragma unroll 4
+      for (int c = c0; c < c0 + NT * 4; ++c) {
+        const int col = n0 + c;
+        if (col < n_valid) argmax_better(bv, bi, bf2f(f2bf(tl[rr * TP + c])), col);
+      }
+#pragma unroll
+      for (int o = 1; o <= 2; o <<= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        argmax_better(bv, bi, ov, oi);
+      }
+      if ((tid & 3) == 0 && rr < M) {
+        pv[(size_t)rr * ntiles + tile] = bv;
+        pi[(size_t)rr * ntiles + tile] = bi;
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < MT * NT; ++e) {
+    const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
+    const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
+    const int nt = q % NT, m = q / NT;
+    const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
+    if (row >= M) continue;
+    if constexpr (EPI == EPI_GLU) {
+      // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns later, both
+      // rounded to bf16 first, as the unfused bf16 GEMM output
+      if ((ln & 8) == 0) {
+        const float gb = bf2f(f2bf(sum_k(m, nt, ln, r))), ub = bf2f(f2bf(sum_k(m, nt, ln + 8, r)));
+        Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_f(gb) * ub);
+      }
+    } else {
+      P[((size_t)slice * M + row) * N + col] = sum_k(m, nt, ln, r);
+    }
+  }
+}
+
+constexpr int MR4 = 32;   // rows of the MXFP4 ring kernel (MT <= 2)
+
+bool shape4_ok(int M, int N, int K, int S, int bn) {
+  return M >= 1 && M <= MR4 && N >= bn && N % bn == 0 && S >= 1 && K % S == 0 && (K / S) >= NS * BK4 &&
+         (K / S) % (NS * BK4) == 0;
+}
+
+bool ptrs4_ok(const void* X, const void* Wq, const void* E) {
+  return X && Wq && E && docqa_aligned16(X) && docqa_aligned16(Wq) && docqa_aligned16(E);
+}
+
+template <int EPI, int NT>
+void launch4(dim3 grid, hipStream_t s, const void* x, const void* w, const void* e, uint16_t* y, float* p, int M,
+             int N, int K, int Ks, float* pv = nullptr, int* pi = nullptr, int nv = 0) {
+  const int S = grid.y;
+  const int xr = (xcd_knob() && S > 1 && 8 % S == 0 && (grid.x * S) % 8 == 0) ? 1 : 0;
+  const uint16_t* xp = (const uint16_t*)x;
+  const uint8_t* wp = (const uint8_t*)w;
+  const uint8_t* ep = (const uint8_t*)e;
+  if (M <= 16) dgemm4_kernel<EPI, 1, NT><<<grid, 256, 0, s>>>(xp, wp, ep, y, p, M, N, K, Ks, xr, pv, pi, nv);
+  else dgemm4_kernel<EPI, 2, NT><<<grid, 256, 0, s>>>(xp, wp, ep, y, p, M, N, K, Ks, xr, pv, pi, nv);
+}
+}  // namespace
+
+// 2..32-row decode projections over MXFP4 weights (see dgemm4_kernel; one row works too, the
+// plans send it to the GEMV): Wq [N, K / 2] e2m1 code pairs, E [N, K / 32] e8m0 block scales.
+// All return -1, launching nothing, for a shape without an instantiation: more than 32 rows,
+// N % tile, a K slice that is not whole 2048-deep ring turns, pointers off 16 B.
+// fp32 slabs P [S, M, N]; tile_rows: 64, or 32 | 16 (NT = 2 | 1: the same stage per weight row in
+// a ring of 32 | 16 KB) for the narrow projections, whose 64-row tiles times the few slices a
+// 2048-deep granule allows leave CUs idle (O 4096 x 4096: 64 x 2 workgroups)
+int docqa_dgemm4_partial(const void* X, const void* Wq, const void* E, float* P, int M, int N, int K, int S,
+                         int tile_rows, hipStream_t s) {
+  if (M == 0) return 0;
+  if (!P || (tile_rows != 64 && tile_rows != 32 && tile_rows != 16) || !shape4_ok(M, N, K, S, tile_rows) ||
+      !ptrs4_ok(X, Wq, E))
+    return -1;
+  const dim3 grid(N / tile_rows, S);
+  if (tile_rows == 64) launch4<EPI_PARTIAL, 4>(grid, s, X, Wq, E, nullptr, P, M, N, K, K / S);
+  else if (tile_rows == 32) launch4<EPI_PARTIAL, 2>(grid, s, X, Wq, E, nullptr, P, M, N, K, K / S);
+  else launch4<EPI_PARTIAL, 1>(grid, s, X, Wq, E, nullptr, P, M, N, K, K / S);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// Y [M, N / 2] = silu(gate) * up for the 8-interleaved gate|up codes (N = 2 I); 112-row tiles
+// where they give >= 192 workgroups (as docqa_dgemm_glu), else 64-row tiles
+int docqa_dgemm4_glu(const void* X, const void* Wq, const void* E, void* Y, int M, int N, int K, hipStream_t s) {
+  if (M == 0) return 0;
+  if (!Y || !ptrs4_ok(X, Wq, E)) return -1;
+  if (shape4_ok(M, N, K, 1, 112) && N / 112 >= 192)
+    launch4<EPI_GLU, 7>(dim3(N / 112), s, X, Wq, E, (uint16_t*)Y, nullptr, M, N, K, K);
+  else if (shape4_ok(M, N, K, 1, 64))
+    launch4<EPI_GLU, 4>(dim3(N / 64), s, X, Wq, E, (uint16_t*)Y, nullptr, M, N, K, K);
+  else
+    return -1;
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}
+
+// LM head + greedy pick: out[M] = argmax over the first n_valid columns of bf16(X . W'^T), outv[M]
+// the picked value; ws_v / ws_i: [M, N / 64] per-tile partials
+int docqa_dgemm4_argmax(const void* X, const void* Wq, const void* E, int64_t* out, float* outv, float* ws_v,
+                        int* ws_i, int M, int N, int K, int n_valid, hipStream_t s) {
+  if (M == 0) return 0;
+  if (!out || !ws_v || !ws_i || !shape4_ok(M, N, K, 1, 64) || n_valid <= 0 || n_valid > N || !ptrs4_ok(X, Wq, E))
+    return -1;
+  launch4<EPI_ARGMAX, 4>(dim3(N / 64), s, X, Wq, E, nullptr, nullptr, M, N, K, K, ws_v, ws_i, n_valid);
+  argmax_merge_kernel<<<M, 256, 0, s>>>(ws_v, ws_i, N / 64, out, outv);
+  DOCQA_CHECK_LAUNCH();
+  return 0;
+}

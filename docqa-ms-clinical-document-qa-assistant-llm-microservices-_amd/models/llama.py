@@ -404,9 +404,11 @@ class LlamaModel:
         # dgemm8_glu_ok); the rest, and every other step shape, run on the bf16 image W'
         use8 = (not meta.prefill and self.fp8 is not None and x.is_cuda
                 and 1 <= M <= ops.DGEMM8_MAX_ROWS)
-        # one-row decode steps of a quantize_mxfp4() model stream the MXFP4 copies the same way
-        # (ops.gemv4_plan / gemv4_glu_ok); a model holds one streamed format, w8 lists its projections
-        use4 = not meta.prefill and self.mx4 is not None and x.is_cuda and M == 1
+        # decode steps of 1..ops.DGEMM4_MAX_ROWS rows of a quantize_mxfp4() model stream the MXFP4
+        # copies the same way (one row: ops.gemv4_plan / gemv4_glu_ok, 2..32 rows: the ring kernel,
+        # ops.dgemm4_plan / dgemm4_glu_ok); a model holds one streamed format, w8 lists its projections
+        use4 = (not meta.prefill and self.mx4 is not None and x.is_cuda
+                and 1 <= M <= ops.DGEMM4_MAX_ROWS)
         wq = self.mx4 if use4 else self.fp8
         w8: dict = {}
         # a short prefill (<= ops.MID_M_MAX prompt tokens: batch-1 serving) has the decode
@@ -447,6 +449,12 @@ class LlamaModel:
                     w8[k] = (S8, t8)
                     plans[k] = (S8, lambda a, w, S=S8, t=t8: ops.dgemm8_partial(a, w[0], w[1], S, t))
                     continue
+                S4, t4 = ops.dgemm4_plan(M, *L0[k].shape) if use4 else (0, 64)
+                if S4:
+                    # 2..32 rows, MXFP4 weights: the ring kernel over the (q, e) copy
+                    w8[k] = (S4, t4)
+                    plans[k] = (S4, lambda a, w, S=S4, t=t4: ops.dgemm4_partial(a, w[0], w[1], S, t))
+                    continue
                 Sg, R = ops.gemv_plan(M, *L0[k].shape) if x.is_cuda else (0, 0)
                 if Sg:
                     # one row: the register-streaming GEMV (no LDS ring) -- QKV / O
@@ -479,6 +487,9 @@ class LlamaModel:
             elif use8 and ops.dgemm8_glu_ok(M, *L0["gate_up"].shape):
                 w8["gate_up"] = (1, 0)
                 glu = lambda a, w: ops.dgemm8_glu(a, w[0], w[1])  # noqa: E731
+            elif use4 and ops.dgemm4_glu_ok(M, *L0["gate_up"].shape):
+                w8["gate_up"] = (1, 0)
+                glu = lambda a, w: ops.dgemm4_glu(a, w[0], w[1])  # noqa: E731
             elif decode and x.is_cuda and ops.gemv_glu_ok(M, *L0["gate_up"].shape):
                 glu = ops.gemv_glu        # one row: the register-streaming GEMV with SwiGLU
             elif small and (ops.pgemm_ok(M, *L0["gate_up"].shape)

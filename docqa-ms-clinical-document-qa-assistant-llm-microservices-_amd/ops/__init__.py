@@ -549,12 +549,17 @@ def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False,
     step too where :func:`dgemm8_argmax_ok` (dgemm8_kernel EPI_ARGMAX).
     ``mxfp4``: the (q, e) MXFP4 copy of ``w`` (:func:`quantize_mxfp4_rows`, ``w`` its exact
     image) -- a one-row step streams the codes where :func:`gemv4_argmax_ok` (gemv4_kernel
-    EPI_ARGMAX); every other step runs on ``w``."""
+    EPI_ARGMAX), a 2..32-row step where :func:`dgemm4_argmax_ok` (dgemm4_kernel EPI_ARGMAX); every
+    other step runs on ``w``."""
     if _gpu(x):
         N, K = w.shape
         if mxfp4 is not None and n_valid > 0 and gemv4_argmax_ok(x.numel() // K, N, K):
             R, lb, kw = _GEMV4_EPI[K]
             ids, vals = _native().gemv4_argmax_val(x.contiguous(), mxfp4[0], mxfp4[1], int(n_valid), R, lb, kw)
+            return (ids, vals) if with_values else ids
+        if mxfp4 is not None and n_valid > 0 and dgemm4_argmax_ok(x.numel() // K, N, K):
+            # 2..32 rows: the ring kernel over the codes (dgemm.hip dgemm4_kernel EPI_ARGMAX)
+            ids, vals = _native().dgemm4_argmax_val(x.contiguous(), mxfp4[0], mxfp4[1], int(n_valid))
             return (ids, vals) if with_values else ids
         if fp8 is not None and n_valid > 0 and gemv8_argmax_ok(x.numel() // K, N, K):
             R, lb = _GEMV8_EPI[K]
@@ -980,6 +985,98 @@ def dgemm8_glu(x, q, s):
     if _gpu(x):
         return _native().dgemm8_glu(x.contiguous(), q, s)
     return glu_linear(x, dequantize_fp8_rows(q, s, x.dtype))
+
+
+# 2..DGEMM4_MAX_ROWS-row decode steps over the MXFP4 (q, e) copies (dgemm.hip dgemm4_kernel: the
+# same ring, 512 codes per weight row per stage -- K slices of whole 2048-deep ring turns, block
+# scales applied while widening; slab tiles of 64, 32 or 16 weight rows).  33+ rows stay on W', as
+# with FP8.
+DGEMM4_MAX_ROWS = 32
+DGEMM4_K = 2048
+_DGEMM4 = os.environ.get("DOCQA_DGEMM4", "1") != "0"
+# (N, K) -> decode buckets (powers of two, engine/llm_engine.py:_bucket) whose step takes the MXFP4
+# ring kernel: slab projections (bucket -> (split-K count, weight rows per workgroup); a plain
+# tuple of buckets means ops.dgemm4_splits at 64 rows), the fused-SwiGLU gate|up, the LM head +
+# argmax.  A (shape, bucket) pair is listed only where benchmarks/bench_dgemm_mxfp4.py measured the
+# listed variant's median below the shipped bf16 plan's with disjoint min..max window ranges, in
+# BOTH runs of profiles/mxfp4_dgemm_probe.log.  The comparison is against bf16 only: inside an
+# MXFP4 model W' is the only alternative (the log's FP8 column is for the README).  Everything
+# else keeps streaming W'.
+# Llama-3-8B / Mistral-7B at M = 2 / 8 / 16, MXFP4 vs bf16 us (second run): QKV (32-row tiles, S = 1:
+# 192 workgroups where 64-row tiles give 96 x 2) 7.2 / 8.4 / 10.1 vs 12.2 / 12.5 / 12.6, O (32-row
+# tiles, S = 2: 256 workgroups, 64-row tiles only 128) 6.2 / 6.7 vs 8.9 / 8.7, gate|up 19.2 /
+# 21.0 / 23.3 vs 48.5 / 47.5 / 48.0 (31.7 vs 49.5 at 32), down (S = 7) 13.7 / 15.2 / 19.1 vs 21.2 /
+# 21.1 / 20.9, LM head 70.5 / 84.2 / 107.4 vs 190.9 / 187.4 / 188.4 (145.1 vs 192.6 at 32; Mistral
+# 24.8 / 28.1 / 33.8 / 43.7 vs 57.3 / 58.0 / 58.7 / 59.9).
+# Losers, which stay on W': every slab projection at bucket 32 (two m-tiles: each of the two
+# k-groups widens every fragment again; QKV 14.2 vs 13.7, O 10.8 vs 9.7, down 22.8 vs 21.9) and O
+# at bucket 16 (7.7 vs 8.9 in the median, but one window of the second run reached into bf16's
+# range).  The llama3-1b-test preset's rows are the suite's model, no served model has them: its
+# O 2048 x 2048 lost or tied everywhere (5.4 vs 5.4 at 8) and stays on W'; its QKV 3072 x 2048
+# won at buckets 4 and 8 only (5.4 / 5.8 vs 6.0 / 6.2), its down 2048 x 8192 at 2, 4 and 16 (bucket
+# 8: 7.2 vs 9.3, one outlier window overlapping).
+_B4 = (2, 4, 8, 16, 32)
+_DGEMM4_SLAB: dict = {(6144, 4096): {b: (1, 32) for b in (2, 4, 8, 16)},
+                      (4096, 4096): {b: (2, 32) for b in (2, 4, 8)},
+                      (4096, 14336): {b: (7, 64) for b in (2, 4, 8, 16)},
+                      (3072, 2048): {b: (1, 32) for b in (4, 8)},
+                      (2048, 8192): {b: (4, 32) for b in (2, 4, 16)}}
+_DGEMM4_GLU: dict = {(28672, 4096): _B4, (16384, 2048): _B4}
+_DGEMM4_LM: dict = {(128256, 4096): _B4, (32768, 4096): _B4, (32000, 2048): _B4}
+
+
+def _dgemm4_listed(table: dict, M: int, N: int, K: int) -> bool:
+    if not _DGEMM4 or not (2 <= M <= DGEMM4_MAX_ROWS) or N % 64 or K % DGEMM4_K:
+        return False
+    return (1 << (M - 1).bit_length()) in table.get((N, K), ())
+
+
+def dgemm4_splits(N: int, K: int, tile: int = 64, min_wgs: int = 192) -> int:
+    """:func:`dgemm8_splits` on the MXFP4 ring's K granule: the smallest S (slices of whole
+    2048-deep ring turns) giving >= ``min_wgs`` workgroups, else the most slices there are; 0
+    where K is not whole ring turns."""
+    if N % tile or K % DGEMM4_K or K < DGEMM4_K:
+        return 0
+    turns = K // DGEMM4_K
+    cands = [S for S in range(1, turns + 1) if turns % S == 0]
+    return next((S for S in cands if (N // tile) * S >= min_wgs), cands[-1])
+
+
+def dgemm4_plan(M: int, N: int, K: int) -> tuple[int, int]:
+    """(split-K count, weight rows per workgroup) of the MXFP4-weight ring kernel for a 2..32-row
+    decode projection; (0, 64) where the shape has no instantiation or the probe did not show it
+    faster than the bf16 plan (the caller then streams W').  DOCQA_DGEMM4=0 disables."""
+    if not _dgemm4_listed(_DGEMM4_SLAB, M, N, K):
+        return 0, 64
+    entry = _DGEMM4_SLAB[(N, K)]
+    if isinstance(entry, dict):      # bucket -> (split-K count, tile rows) the probe picked
+        return entry[1 << (M - 1).bit_length()]
+    return dgemm4_splits(N, K), 64
+
+
+def dgemm4_glu_ok(M: int, N: int, K: int) -> bool:
+    """The 2..32-row gate|up projection with SwiGLU on the MXFP4-weight ring kernel."""
+    return _dgemm4_listed(_DGEMM4_GLU, M, N, K)
+
+
+def dgemm4_argmax_ok(M: int, N: int, K: int) -> bool:
+    """The 2..32-row LM head + greedy pick on the MXFP4-weight ring kernel."""
+    return _dgemm4_listed(_DGEMM4_LM, M, N, K)
+
+
+def dgemm4_partial(x, q, e, splits: int, tile_rows: int = 64):
+    """fp32 slabs [S, M, N] of x @ W'^T for 2..32 rows on the MXFP4-weight ring kernel
+    (:func:`dgemm4_plan`)."""
+    if _gpu(x):
+        return _native().dgemm4_partial(x.contiguous(), q, e, int(splits), int(tile_rows))
+    return dgemm_partial(x, dequantize_mxfp4_rows(q, e, x.dtype), splits, tile_rows)
+
+
+def dgemm4_glu(x, q, e):
+    """silu(x Wg^T) * (x Wu^T) for 2..32 rows over MXFP4 8-interleaved gate|up weights."""
+    if _gpu(x):
+        return _native().dgemm4_glu(x.contiguous(), q, e)
+    return glu_linear(x, dequantize_mxfp4_rows(q, e, x.dtype))
 
 
 NORM_FUSE_ROWS = 4
