@@ -394,9 +394,20 @@ at::Tensor sample(const at::Tensor& logits, const at::Tensor& inv_temp, const at
   CHECK_GPU(logits);
   TORCH_CHECK(logits.scalar_type() == at::kFloat && logits.dim() == 2 && logits.stride(1) == 1,
               "sample wants fp32 [rows, V]");
-  CHECK_I32(top_k);
+  // per-row parameters: the engine passes bucket-sized tensors for fewer rows, so >= rows
+  const int64_t rows = logits.size(0);
+  const auto check_row_param = [&](const at::Tensor& t, at::ScalarType ty, const char* name) {
+    TORCH_CHECK(t.scalar_type() == ty, "sample: ", name, " must be ", ty == at::kInt ? "int32" : "fp32");
+    TORCH_CHECK(t.device() == logits.device(), "sample: ", name, " must be on the logits' device");
+    TORCH_CHECK(t.is_contiguous(), "sample: ", name, " must be contiguous");
+    TORCH_CHECK(t.numel() >= rows, "sample: ", name, " has ", t.numel(), " entries for ", rows, " rows");
+  };
+  check_row_param(inv_temp, at::kFloat, "inv_temp");
+  check_row_param(top_k, at::kInt, "top_k");
+  check_row_param(top_p, at::kFloat, "top_p");
+  check_row_param(u, at::kFloat, "u");
   c10::DeviceGuard g(logits.device());
-  auto out = at::empty({logits.size(0)}, logits.options().dtype(at::kLong));
+  auto out = at::empty({rows}, logits.options().dtype(at::kLong));
   CHECK_RC(docqa_sample(logits.data_ptr<float>(), logits.size(0), logits.size(1), logits.stride(0),
                         inv_temp.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
                         u.data_ptr<float>(), out.data_ptr<int64_t>(), stream()), "sample");

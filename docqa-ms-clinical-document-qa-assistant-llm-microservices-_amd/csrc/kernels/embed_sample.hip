@@ -204,7 +204,9 @@ __global__ __launch_bounds__(64) void argmax_pass2(const float* __restrict__ pv,
 // the temperature by the caller or by `inv_temp` here).  top-k is applied by a
 // threshold search (bisection on the value range, 24 rounds, no sort); top-p by a
 // second bisection on the probability mass of the survivors.  Then an inverse-CDF
-// draw with the caller's uniform u[row].
+// draw with the caller's uniform u[row] over the kept tokens in index order.  Ties at a
+// threshold are all kept; a row with top_k == 1 is an argmax (lowest index of the maximum).
+// Logits must be finite: the bisections work on the row's [min, max] range.
 __device__ float block_sum(float v, float* sh) {
   v = wave_sum(v);
   __syncthreads();
@@ -230,13 +232,35 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* __restrict__ l
   const int row = blockIdx.x;
   const float* r = logits + (size_t)row * ld;
   const float it = inv_temp[row];
+  const int k = top_k[row];
+  if (k == 1) {
+    // greedy row inside a sampled batch: the lowest index of the maximum, whatever u and
+    // top_p are (the tie rule of argmax_pass1; a threshold would keep every copy of the
+    // maximum and let u pick among them).  k is per row, so the branch is uniform.
+    float bv = -FLT_MAX;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < V; i += 256) better(bv, bi, r[i] * it, i);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      better(bv, bi, ov, oi);
+    }
+    __shared__ int si[4];
+    if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 1; w < 4; ++w) better(bv, bi, sh[w], si[w]);
+      out[row] = bi == 0x7fffffff ? 0 : bi;   // all-NaN row: a valid id
+    }
+    return;
+  }
   float mx = -FLT_MAX, mn = FLT_MAX;
   for (int i = threadIdx.x; i < V; i += 256) { const float x = r[i] * it; mx = fmaxf(mx, x); mn = fminf(mn, x); }
   mx = block_max(mx, sh);
   mn = -block_max(-mn, sh);
   // top-k threshold: largest th such that count(x >= th) >= k
   float th = -FLT_MAX;
-  const int k = top_k[row];
   if (k > 0 && k < V) {
     float lo = mn, hi = mx;
     for (int it2 = 0; it2 < 24; ++it2) {

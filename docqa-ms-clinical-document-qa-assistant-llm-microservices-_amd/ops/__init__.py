@@ -1220,6 +1220,25 @@ def token_cls_argmax(h, w, bias, n_valid: int):
 
 
 def sample(logits, inv_temp, top_k, top_p, u):
+    """One token id per row of ``logits`` [rows, V] from temperature / top-k / top-p sampling.
+
+    ``inv_temp``, ``top_p``, ``u`` are fp32 and ``top_k`` int32, one entry per row (contiguous,
+    on the logits' device, at least ``rows`` long: a longer bucket-sized tensor is fine).  Per row,
+    with ``x = float32(logit) * inv_temp``:
+
+    * top-k (``0 < top_k < V``) keeps ``x >=`` the k-th largest value; ties at that value are all kept.
+    * top-p (``0 < top_p < 1``) then keeps, of the survivors by descending probability, the shortest
+      prefix whose mass reaches ``top_p`` of theirs; ties at the cutoff value are all kept.
+    * The draw is the inverse CDF of the kept tokens **in vocabulary-index order** at ``u`` in
+      [0, 1): the first kept token whose cumulative share exceeds ``u``.  A dropped token is never
+      returned.
+    * ``top_k == 1`` is an argmax: the lowest index of the maximum of ``x``, whatever ``u`` and
+      ``top_p`` are -- the tie rule of every greedy path, so on the same logits a greedy row gets the
+      same token inside a sampled batch as alone.
+
+    Logits are expected finite (NaN / inf are not handled: the thresholds are searched over the
+    row's [min, max] range) and ``inv_temp`` positive.
+    """
     if _gpu(logits):
         return _native().sample(logits.float().contiguous(), inv_temp, top_k, top_p, u)
     return ref.sample(logits, inv_temp, top_k, top_p, u)

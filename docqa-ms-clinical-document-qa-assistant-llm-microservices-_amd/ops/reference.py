@@ -276,6 +276,9 @@ def sample(logits, inv_temp, top_k, top_p, u):
     for r in range(logits.shape[0]):
         x = logits[r].float() * float(inv_temp[r])
         k = int(top_k[r])
+        if k == 1:      # greedy row: the lowest index of the maximum, whatever u and top_p are
+            out[r] = int(torch.nonzero(x == x.max())[0])
+            continue
         if 0 < k < x.numel():
             th = torch.topk(x, k).values[-1]
             x = torch.where(x >= th, x, torch.full_like(x, -math.inf))
@@ -288,9 +291,11 @@ def sample(logits, inv_temp, top_k, top_p, u):
             mask[si[keep]] = True
             p = torch.where(mask, p, torch.zeros_like(p))
             p = p / p.sum()
+        # first index whose cumulative mass exceeds u: a dropped token (p == 0) never
+        # satisfies that, and a u the rounded total falls short of takes the last kept token
         c = torch.cumsum(p, 0)
-        idx = int(torch.searchsorted(c, torch.tensor([float(u[r])], device=c.device)).clamp(max=x.numel() - 1))
-        out[r] = idx
+        idx = int(torch.searchsorted(c, torch.tensor([float(u[r])], device=c.device), right=True))
+        out[r] = min(idx, int(torch.nonzero(p > 0)[-1]))
     return out
 
 
