@@ -29,6 +29,7 @@ import math
 import os
 import zlib
 from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -143,6 +144,31 @@ class AttnMeta:
     decode_inline: bool = False
 
 
+class Streamed(NamedTuple):
+    """A model's streamed weight copy: the format (a key of ops.STREAMED), per layer
+    {projection: pair} and the LM head's pair -- (q, s) for FP8, (q, e) for MXFP4."""
+    fmt: str
+    layers: list
+    lm_head: tuple
+
+
+@dataclass
+class StepPlan:
+    """Which kernel every projection of one forward runs (LlamaModel._step_plan): plain data.  The
+    families "streamed_gemv" / "streamed_ring" read the streamed pair (ops.streamed_plan's kinds);
+    "gemv", "mgemm", "dgemm", "pgemm" (ops.<family>_partial) and "linear32" the bf16 weights."""
+    # "qkv" | "o" | "down" -> (family, split-K count, rows | tile | cfg, bf16 slabs); absent or
+    # split-K count 0: the library GEMM with the plain consumer
+    proj: dict = field(default_factory=dict)
+    glu: tuple = ("prefill_glu",)       # gate|up: ("streamed_" + kind,) | (bf16 ops wrapper, *arguments)
+    streamed: dict = field(default_factory=dict)    # projections on the streamed pair -> kind
+    nf: dict = field(default_factory=dict)          # "o" | "down" -> splits, add + RMSNorm in-kernel
+    xn: bool = False                                # gate|up and QKV build their input row in-kernel
+
+    def splits(self, k: str) -> int:
+        return self.proj[k][1] if k in self.proj else 0
+
+
 class LlamaModel:
     def __init__(self, cfg: LlamaConfig, device="cuda", dtype=torch.bfloat16, seed: int = 0,
                  init: bool = True):
@@ -171,12 +197,8 @@ class LlamaModel:
         self.layers: list[dict] = []
         self._tick = None      # decode attention's last-arriver merge tickets (ops.decode_ticket)
         self._ntick = None     # fused projection + add + RMSNorm ticket word (ops.dgemm_add_rmsnorm)
-        # FP8 weight copies (quantize_fp8): per layer {name: (q, s)} and the LM head's (q, s)
-        self.fp8: list[dict] | None = None
-        self.lm_head_fp8 = None
-        # MXFP4 weight copies (quantize_mxfp4): per layer {name: (q, e)} and the LM head's (q, e)
-        self.mx4: list[dict] | None = None
-        self.lm_head_mx4 = None
+        # the streamed weight copy (quantize_fp8 / quantize_mxfp4): a model holds one format at most
+        self.streamed: Streamed | None = None
         if init:
             self._random_init(seed)
 
@@ -286,7 +308,8 @@ class LlamaModel:
                        p + "post_attention_layernorm.weight": L["post_norm"]})
         return {k: t.detach().cpu() for k, t in sd.items()}
 
-    FP8_WEIGHTS = ("qkv", "o", "gate_up", "down")
+    STREAMED_WEIGHTS = ("qkv", "o", "gate_up", "down")
+    FP8_WEIGHTS = STREAMED_WEIGHTS      # the name the weight tests read
 
     def quantize_fp8(self) -> None:
         """FP8 weight streaming for decode steps of 1..ops.DGEMM8_MAX_ROWS rows (TP = 1; one row:
@@ -299,25 +322,8 @@ class LlamaModel:
         norms stay as they are.  The copies cost memory (about +50 % of the projections)
         and save none.  Call after random init or load_state_dict_hf, before any decode graph
         is captured."""
-        if self.tp != 1:
-            raise ValueError("FP8 weights need tp_size == 1: per-row scales of the row-parallel O / down shards "
-                             "would depend on the shard's K range and break the TP-invariant weights")
-        if self.mx4 is not None:
-            raise ValueError("quantize_mxfp4() was already applied: one model holds one streamed weight format")
-        if self.fp8 is not None:
-            return
-        fp8 = []
-        for L in self.layers:
-            d = {}
-            for k in self.FP8_WEIGHTS:
-                q, s = ops.quantize_fp8_rows(L[k])
-                L[k] = ops.dequantize_fp8_rows(q, s, self.dtype)
-                d[k] = (q, s)
-            fp8.append(d)
-        q, s = ops.quantize_fp8_rows(self.lm_head)
-        self.lm_head = ops.dequantize_fp8_rows(q, s, self.dtype)
-        self.lm_head_fp8 = (q, s)
-        self.fp8 = fp8
+        self._quantize("fp8-e4m3", "FP8 weights need tp_size == 1: per-row scales of the row-parallel O / down "
+                       "shards would depend on the shard's K range and break the TP-invariant weights")
 
     def quantize_mxfp4(self) -> None:
         """MXFP4 weight streaming for one-row decode steps (TP = 1; the GEMV, where its plan lists
@@ -329,47 +335,196 @@ class LlamaModel:
         relative L2 norm for Gaussian weights -- an opt-in latency / quality trade.  The copies
         cost memory (about +27 % of the projections) and save none.  Call after random init or
         load_state_dict_hf, before any decode graph is captured."""
+        self._quantize("mxfp4", "MXFP4 weights need tp_size == 1: the block scales along K would survive a "
+                       "row-parallel split at multiples of 32, but the tensor-parallel path is neither "
+                       "built nor tested")
+
+    def _quantize(self, fmt: str, tp_error: str) -> None:
+        """Every projection and the LM head get a copy in format ``fmt`` (ops.STREAMED) and are
+        replaced by its exact image."""
         if self.tp != 1:
-            raise ValueError("MXFP4 weights need tp_size == 1: the block scales along K would survive a "
-                             "row-parallel split at multiples of 32, but the tensor-parallel path is neither "
-                             "built nor tested")
-        if self.fp8 is not None:
-            raise ValueError("quantize_fp8() was already applied: one model holds one streamed weight format")
-        if self.mx4 is not None:
-            return
-        mx4 = []
+            raise ValueError(tp_error)
+        if self.streamed is not None:
+            if self.streamed.fmt == fmt:
+                return
+            entry = {"fp8-e4m3": "quantize_fp8", "mxfp4": "quantize_mxfp4"}[self.streamed.fmt]
+            raise ValueError(f"{entry}() was already applied: one model holds one streamed weight format")
+        f = ops.STREAMED[fmt]
+        layers = []
         for L in self.layers:
             d = {}
-            for k in self.FP8_WEIGHTS:
-                q, e = ops.quantize_mxfp4_rows(L[k])
-                L[k] = ops.dequantize_mxfp4_rows(q, e, self.dtype)
-                d[k] = (q, e)
-            mx4.append(d)
-        q, e = ops.quantize_mxfp4_rows(self.lm_head)
-        self.lm_head = ops.dequantize_mxfp4_rows(q, e, self.dtype)
-        self.lm_head_mx4 = (q, e)
-        self.mx4 = mx4
-        if self.device.type == "cuda":
+            for k in self.STREAMED_WEIGHTS:
+                d[k] = f.quantize(L[k])
+                L[k] = f.dequantize(*d[k], self.dtype)
+            layers.append(d)
+        head = f.quantize(self.lm_head)
+        self.lm_head = f.dequantize(*head, self.dtype)
+        self.streamed = Streamed(fmt, layers, head)
+        if fmt == "mxfp4" and self.device.type == "cuda":
             # the quantizer's fp32 temporaries (gigabytes for the LM head) go back to the driver:
             # the engine sizes the KV pool from the HBM that is free after the weights
             torch.cuda.empty_cache()
 
+    def _held(self, fmt: str, part: str):
+        s = self.streamed
+        return getattr(s, part) if s is not None and s.fmt == fmt else None
+
+    # the copies by format (None unless the model streams that format), as tests and probes read them
+    fp8 = property(lambda self: self._held("fp8-e4m3", "layers"))
+    lm_head_fp8 = property(lambda self: self._held("fp8-e4m3", "lm_head"))
+    mx4 = property(lambda self: self._held("mxfp4", "layers"))
+    lm_head_mx4 = property(lambda self: self._held("mxfp4", "lm_head"))
+
     @property
     def weight_format(self) -> str:
-        return "fp8-e4m3" if self.fp8 is not None else "mxfp4" if self.mx4 is not None else "bf16"
+        return self.streamed.fmt if self.streamed is not None else "bf16"
 
     def weight_bytes(self) -> int:
         n = self.embed.numel() + self.lm_head.numel() + self.final_norm.numel()
         for L in self.layers:
             n += sum(t.numel() for t in L.values())
         n *= self.embed.element_size()
-        if self.fp8 is not None:   # the FP8 copies are held next to the bf16 image
-            for q, s in [self.lm_head_fp8] + [t for d in self.fp8 for t in d.values()]:
-                n += q.numel() * q.element_size() + s.numel() * s.element_size()
-        if self.mx4 is not None:   # the MXFP4 copies (codes + block scales), likewise
-            for q, e in [self.lm_head_mx4] + [t for d in self.mx4 for t in d.values()]:
-                n += q.numel() * q.element_size() + e.numel() * e.element_size()
+        if self.streamed is not None:   # the copies (codes + scales) are held next to the bf16 image
+            for pair in [self.streamed.lm_head] + [p for d in self.streamed.layers for p in d.values()]:
+                n += sum(t.numel() * t.element_size() for t in pair)
         return n
+
+    # ------------------------------------------------------------------ step plan
+    def _step_plan(self, M: int, meta: AttnMeta, on_gpu: bool, kv8: bool, fused_attn: bool = False) -> StepPlan:
+        """The kernels of a forward over M rows, from shapes, ``meta`` fields, ``self.tp`` and the
+        module flags alone (no tensor data).  ``on_gpu``: the step's tensors are device tensors;
+        ``kv8``: FP8 KV cache; ``fused_attn``: the per-row decode attention reads the QKV slabs
+        itself (ops.fused_decode_ok of the cache).  Decode steps stream every weight once: per
+        projection a split-K kernel emits slabs straight into the fused consumers (RoPE + KV write
+        for QKV, (TP all-reduce +) residual add + RMSNorm for O / down); steps of 1..max_rows rows
+        of a quantized model read its streamed copy where the format's plans list a kernel
+        (ops.streamed_plan / streamed_glu_kind), everything else the bf16 image W'."""
+        plan = StepPlan()
+        decode = not meta.prefill
+        shape = {k: tuple(self.layers[0][k].shape) for k in self.STREAMED_WEIGHTS}
+        s = self.streamed
+        fmt = s.fmt if (decode and s is not None and on_gpu and 1 <= M <= ops.STREAMED[s.fmt].max_rows) else ""
+        # a short prefill (<= ops.MID_M_MAX prompt tokens: batch-1 serving) has the decode
+        # step's shape -- too few rows for the 256 x 256 prefill GEMM's tiles -- so it takes
+        # the same split-K projection plans and fused consumers (RoPE + KV write, add + norm)
+        # (ops.prefill_route mirrors the prefill plan choices below for the GEMM probes and
+        # tests/test_pgemm_gpu.py::test_prefill_route_products -- keep the two in step)
+        small = not decode and on_gpu and _PREFILL_MID and M <= ops.MID_M_MAX
+        if decode or small:
+            # bf16 split-K slabs (ops.SLAB_BF16) where the consumer is the RoPE + cache-write
+            # kernel (QKV) or the TP = 1 add + RMSNorm (O / down); the fused attention kernels
+            # that read QKV slabs themselves take fp32 only
+            s16 = on_gpu and self.tp == 1 and ops.SLAB_BF16
+            if decode and meta.shared_len is not None:      # cascade: the grouped kernel reading the slabs
+                qkv_rope = not (meta.decode_groups is not None and meta.decode_inline and _GROUP_FUSED
+                                and not kv8 and meta.slot_mapping is not None)
+            else:
+                qkv_rope = not (decode and fused_attn)
+            b16 = {"qkv": s16 and qkv_rope, "o": s16, "down": s16}
+            for k in ("qkv", "o", "down"):
+                N, K = shape[k]
+                kind, S, R = ops.streamed_plan(fmt, M, N, K) if fmt else ("", 0, 0)
+                if kind:
+                    # the GEMV or the ring kernel over the streamed pair
+                    plan.streamed[k] = kind
+                    plan.proj[k] = ("streamed_" + kind, S, R, False)
+                    continue
+                S, R = ops.gemv_plan(M, N, K) if on_gpu else (0, 0)
+                if S:
+                    # one row: the register-streaming GEMV (no LDS ring) -- QKV / O
+                    plan.proj[k] = ("gemv", S, R, False)
+                    continue
+                S, c = ops.mid_plan(M, N, K)
+                if S:
+                    plan.proj[k] = ("mgemm", S, c, bool(b16[k] and S > 1))
+                else:
+                    S, t = ops.decode_plan(M, N, K)
+                    plan.proj[k] = ("dgemm", S, t, False)
+            if small and M > 256:
+                # a 257..512-token prefill's down projection (decode buckets keep their plan):
+                # the 256 x 256 kernel's S=8 slabs where K is long -- 8B: 66.1 vs the mid-M
+                # kernel's S=4 77.5 and hipBLASLt's 97.4 us at 512 rows
+                # (profiles/r6_prefill_mid_plans.log); the 70B TP-8 shard keeps mid_plan's
+                Sd = ops.down_small_split(M, *shape["down"])
+                if Sd:
+                    plan.proj["down"] = ("pgemm", Sd, 0, False)
+            N, K = shape["gate_up"]
+            kind = ops.streamed_glu_kind(fmt, M, N, K) if fmt else ""
+            if kind:
+                plan.streamed["gate_up"] = kind
+                plan.glu = ("streamed_" + kind,)
+            elif decode and on_gpu and ops.gemv_glu_ok(M, N, K):
+                plan.glu = ("gemv_glu",)      # one row: the register-streaming GEMV with SwiGLU
+            elif small and (ops.pgemm_ok(M, N, K) or ops.prefill_split_plan(M, N, K, glu=True)):
+                # 256 x 256 tiles with SwiGLU (104 vs 141 us at M = 512), or their split-K
+                # slabs into the SwiGLU consumer where too few tiles (the 70B TP-8 shard)
+                plan.glu = ("prefill_glu",)
+            elif decode and s16 and ops.glu_split16_plan(M, N, K)[0]:
+                plan.glu = ("glu_split16", *ops.glu_split16_plan(M, N, K))
+            else:
+                Sg, cg = ops.mid_plan(M, N, K, glu=True)
+                plan.glu = ("mgemm_glu", cg) if Sg else ("glu_linear",)
+        elif on_gpu:
+            # 513..2048-token prefills: split-K slab plans where they win with the consumer
+            s16 = self.tp == 1 and ops.SLAB_BF16      # bf16 slabs: see the decode plans above
+            for k in ("qkv", "o", "down"):
+                S, c = ops.prefill_plan(M, *shape[k])
+                if S >= 2:
+                    plan.proj[k] = ("mgemm", S, c, bool(s16))
+                elif not S:
+                    # narrow tensor-parallel shards: the 256 x 256 tiles split over K
+                    Sp = ops.prefill_split_plan(M, *shape[k])
+                    if Sp:
+                        plan.proj[k] = ("pgemm", Sp, 0, False)
+        if self.tp > 1 and not on_gpu:
+            # CPU TP rehearsal: row-parallel partials as fp32 slabs, all-reduced before the one
+            # bf16 rounding (comm.tp_add_rmsnorm), so TP = N tracks TP = 1's rounding
+            for k in ("o", "down"):
+                if not plan.splits(k):
+                    plan.proj[k] = ("linear32", 1, 0, False)
+        # batch 1 (<= ops.NORM_FUSE_ROWS rows, TP = 1): O / down with the residual add + RMSNorm
+        # in the projection's own last workgroup -- no add_rmsnorm_splitk launch
+        if decode and self.tp == 1 and on_gpu and not plan.streamed:
+            for k in ("o", "down"):
+                S = ops.dgemm_norm_plan(M, *shape[k])
+                if S:
+                    plan.nf[k] = S
+        # batch 1 (one row, TP = 1, skinny-kernel plans): the gate|up and the next layer's QKV
+        # projection build their input row themselves -- residual add + RMSNorm of the previous
+        # projection's slabs, in LDS, under their first weight stages (dgemm.hip XNormIn) --
+        # so no add_rmsnorm launch runs between projections; the residual ping-pongs between
+        # two buffers (one workgroup writes the new one while the others read the old)
+        plan.xn = bool(decode and self.tp == 1 and not plan.nf and on_gpu
+                       and plan.splits("qkv") and plan.splits("o") and plan.splits("down")
+                       and ops.xn_ok(M, self.cfg.hidden) and not ops.mid_plan(M, *shape["gate_up"], glu=True)[0])
+        return plan
+
+    def _partial(self, p: tuple, a, w):
+        """Split-K slabs of one StepPlan.proj entry: ``a`` times the weight (or streamed pair) ``w``."""
+        fam, S, r, b16 = p
+        if fam.startswith("streamed_"):
+            return ops.streamed_partial(self.streamed.fmt, fam[9:], a, w, S, r)
+        if fam == "gemv":
+            return ops.gemv_partial(a, w, S, r)
+        if fam == "mgemm" and S == 1:
+            return ops.mgemm_partial(a, w, 1, r).float()[None]
+        if fam == "mgemm":
+            return ops.mgemm_partial(a, w, S, r, bf16=b16)
+        if fam == "dgemm":
+            return ops.dgemm_partial(a, w, S, r)
+        if fam == "pgemm":
+            return ops.pgemm_partial(a, w, S)
+        if fam == "linear32":
+            return F.linear(a.float(), w.float())[None]
+        raise ValueError(f"no kernel family {fam!r}")
+
+    def _glu(self, plan: StepPlan, a, w):
+        """silu(a Wg^T) * (a Wu^T) on the kernel of StepPlan.glu: the streamed pair's, or the bf16
+        ops wrapper the plan names (gemv_glu, prefill_glu, glu_split16, mgemm_glu, glu_linear)."""
+        fam, *args = plan.glu
+        if fam.startswith("streamed_"):
+            return ops.streamed_glu(self.streamed.fmt, fam[9:], a, w)
+        return getattr(ops, fam)(a, w, *args)
 
     # ------------------------------------------------------------------ forward
     def forward(self, input_ids: torch.Tensor, meta: AttnMeta, kv_caches: list,
@@ -383,13 +538,6 @@ class LlamaModel:
         h, x = ops.embed_rmsnorm(input_ids, self.embed, self.layers[0]["in_norm"], eps)
         residual = h
         nl = len(self.layers)
-        # decode steps stream every weight once: per projection the mid-M MFMA GEMM
-        # (mgemm.hip, 129..512 rows where it wins -- ops.mid_plan) or the skinny
-        # weight-streaming kernel (dgemm.hip, <= 192 rows -- ops.decode_plan) emits fp32
-        # split-K slabs straight into the fused consumers: RoPE + KV write for QKV, and for the
-        # row-parallel O / down the (TP all-reduce +) residual add + RMSNorm
-        # (comm.tp_add_rmsnorm); split 0 = library GEMM + plain consumer.  Prefill (large M):
-        # the 256 x 256 MFMA GEMM (pgemm.hip) with SwiGLU fused into the gate|up epilogue.
         decode = not meta.prefill
         # an FP8 KV cache is written by rope_cache / rope_cache_splitk only: the attention
         # kernels that fuse RoPE and the new token's cache write store bf16
@@ -397,180 +545,39 @@ class LlamaModel:
         group_fused, cascade_rope = _GROUP_FUSED and not kv8, _CASCADE_ROPE and not kv8
         lin = ops.decode_linear if decode else ops.prefill_linear
         M = x.shape[0]
-        plans = {}
-        # decode steps of 1..ops.DGEMM8_MAX_ROWS rows of a quantize_fp8() model stream the FP8
-        # copies where the plans list a kernel (w8: those projections) -- one row: the GEMV
-        # (ops.gemv8_plan / gemv8_glu_ok), 2..32 rows: the ring kernel (ops.dgemm8_plan /
-        # dgemm8_glu_ok); the rest, and every other step shape, run on the bf16 image W'
-        use8 = (not meta.prefill and self.fp8 is not None and x.is_cuda
-                and 1 <= M <= ops.DGEMM8_MAX_ROWS)
-        # decode steps of 1..ops.DGEMM4_MAX_ROWS rows of a quantize_mxfp4() model stream the MXFP4
-        # copies the same way (one row: ops.gemv4_plan / gemv4_glu_ok, 2..32 rows: the ring kernel,
-        # ops.dgemm4_plan / dgemm4_glu_ok); a model holds one streamed format, w8 lists its projections
-        use4 = (not meta.prefill and self.mx4 is not None and x.is_cuda
-                and 1 <= M <= ops.DGEMM4_MAX_ROWS)
-        wq = self.mx4 if use4 else self.fp8
-        w8: dict = {}
-        # a short prefill (<= ops.MID_M_MAX prompt tokens: batch-1 serving) has the decode
-        # step's shape -- too few rows for the 256 x 256 prefill GEMM's tiles -- so it takes
-        # the same split-K projection plans and fused consumers (RoPE + KV write, add + norm)
-        # (ops.prefill_route mirrors the prefill plan choices below for the GEMM probes and
-        # tests/test_pgemm_gpu.py::test_prefill_route_products -- keep the two in step)
-        small = (not decode and x.is_cuda and _PREFILL_MID and M <= ops.MID_M_MAX)
-        if (decode or small) and self.layers:
-            L0 = self.layers[0]
-            cascade = decode and meta.shared_len is not None
-            # bf16 split-K slabs (ops.SLAB_BF16) where the consumer is the RoPE + cache-write
-            # kernel (QKV) or the TP = 1 add + RMSNorm (O / down); the fused attention kernels
-            # that read QKV slabs themselves take fp32 only
-            s16 = x.is_cuda and self.tp == 1 and ops.SLAB_BF16
-            qkv_rope = (not decode or
-                        (not (meta.decode_groups is not None and meta.decode_inline and group_fused
-                              and meta.slot_mapping is not None) if cascade
-                         else not (meta.block_tables is not None and kv_caches
-                                   and ops.fused_decode_ok(kv_caches[0][0], meta.block_tables))))
-            b16 = {"qkv": s16 and qkv_rope, "o": s16, "down": s16}
-            for k in ("qkv", "o", "down"):
-                S8, R8 = ops.gemv8_plan(M, *L0[k].shape) if use8 else (0, 0)
-                if S8:
-                    # one row, FP8 weights: the same GEMV over the (q, s) copy, half the bytes
-                    w8[k] = (S8, R8)
-                    plans[k] = (S8, lambda a, w, S=S8, R=R8: ops.gemv8_partial(a, w[0], w[1], S, R))
-                    continue
-                S4, R4 = ops.gemv4_plan(M, *L0[k].shape) if use4 else (0, 0)
-                if S4:
-                    # one row, MXFP4 weights: the GEMV over the (q, e) copy, 4.25 bits per weight
-                    w8[k] = (S4, R4)
-                    plans[k] = (S4, lambda a, w, S=S4, R=R4: ops.gemv4_partial(a, w[0], w[1], S, R))
-                    continue
-                S8, t8 = ops.dgemm8_plan(M, *L0[k].shape) if use8 else (0, 64)
-                if S8:
-                    # 2..32 rows, FP8 weights: the ring kernel over the (q, s) copy
-                    w8[k] = (S8, t8)
-                    plans[k] = (S8, lambda a, w, S=S8, t=t8: ops.dgemm8_partial(a, w[0], w[1], S, t))
-                    continue
-                S4, t4 = ops.dgemm4_plan(M, *L0[k].shape) if use4 else (0, 64)
-                if S4:
-                    # 2..32 rows, MXFP4 weights: the ring kernel over the (q, e) copy
-                    w8[k] = (S4, t4)
-                    plans[k] = (S4, lambda a, w, S=S4, t=t4: ops.dgemm4_partial(a, w[0], w[1], S, t))
-                    continue
-                Sg, R = ops.gemv_plan(M, *L0[k].shape) if x.is_cuda else (0, 0)
-                if Sg:
-                    # one row: the register-streaming GEMV (no LDS ring) -- QKV / O
-                    plans[k] = (Sg, lambda a, w, S=Sg, R=R: ops.gemv_partial(a, w, S, R))
-                    continue
-                S, c = ops.mid_plan(M, *L0[k].shape)
-                if S and b16[k] and S > 1:
-                    plans[k] = (S, lambda a, w, S=S, c=c: ops.mgemm_partial(a, w, S, c, bf16=True))
-                elif S:
-                    plans[k] = (S, lambda a, w, S=S, c=c: (ops.mgemm_partial(a, w, S, c) if S > 1
-                                                          else ops.mgemm_partial(a, w, 1, c).float()[None]))
-                else:
-                    S, t = ops.decode_plan(M, *L0[k].shape)
-                    plans[k] = (S, lambda a, w, S=S, t=t: ops.dgemm_partial(a, w, S, t))
-            if small and M > 256 and "down" in plans:
-                # a 257..512-token prefill's down projection (decode buckets keep their plan):
-                # the 256 x 256 kernel's S=8 slabs where K is long -- 8B: 66.1 vs the mid-M
-                # kernel's S=4 77.5 and hipBLASLt's 97.4 us at 512 rows
-                # (profiles/r6_prefill_mid_plans.log); the 70B TP-8 shard keeps mid_plan's
-                Sd = ops.down_small_split(M, *L0["down"].shape)
-                if Sd:
-                    plans["down"] = (Sd, lambda a, w, S=Sd: ops.pgemm_partial(a, w, S))
-            Sg, cg = ops.mid_plan(M, *L0["gate_up"].shape, glu=True)
-            if use8 and ops.gemv8_glu_ok(M, *L0["gate_up"].shape):
-                w8["gate_up"] = (1, 0)
-                glu = lambda a, w: ops.gemv8_glu(a, w[0], w[1])  # noqa: E731
-            elif use4 and ops.gemv4_glu_ok(M, *L0["gate_up"].shape):
-                w8["gate_up"] = (1, 0)
-                glu = lambda a, w: ops.gemv4_glu(a, w[0], w[1])  # noqa: E731
-            elif use8 and ops.dgemm8_glu_ok(M, *L0["gate_up"].shape):
-                w8["gate_up"] = (1, 0)
-                glu = lambda a, w: ops.dgemm8_glu(a, w[0], w[1])  # noqa: E731
-            elif use4 and ops.dgemm4_glu_ok(M, *L0["gate_up"].shape):
-                w8["gate_up"] = (1, 0)
-                glu = lambda a, w: ops.dgemm4_glu(a, w[0], w[1])  # noqa: E731
-            elif decode and x.is_cuda and ops.gemv_glu_ok(M, *L0["gate_up"].shape):
-                glu = ops.gemv_glu        # one row: the register-streaming GEMV with SwiGLU
-            elif small and (ops.pgemm_ok(M, *L0["gate_up"].shape)
-                          or ops.prefill_split_plan(M, *L0["gate_up"].shape, glu=True)):
-                # 256 x 256 tiles with SwiGLU (104 vs 141 us at M = 512), or their split-K
-                # slabs into the SwiGLU consumer where too few tiles (the 70B TP-8 shard)
-                glu = ops.prefill_glu
-            elif decode and s16 and ops.glu_split16_plan(M, *L0["gate_up"].shape)[0]:
-                S2, c2 = ops.glu_split16_plan(M, *L0["gate_up"].shape)
-                glu = lambda a, w, S=S2, c=c2: ops.glu_split16(a, w, S, c)  # noqa: E731
-            else:
-                glu = (lambda a, w: ops.mgemm_glu(a, w, cg)) if Sg else ops.glu_linear
-        else:
-            glu = ops.prefill_glu
-            if self.layers and x.is_cuda and not decode:
-                # 513..2048-token prefills: split-K slab plans where they win with the consumer
-                L0 = self.layers[0]
-                s16 = self.tp == 1 and ops.SLAB_BF16      # bf16 slabs: see the decode plans above
-                for k in ("qkv", "o", "down"):
-                    S, c = ops.prefill_plan(M, *L0[k].shape)
-                    if S >= 2:
-                        plans[k] = (S, lambda a, w, S=S, c=c, b=s16: ops.mgemm_partial(a, w, S, c, bf16=b))
-                    elif not S:
-                        # narrow tensor-parallel shards: the 256 x 256 tiles split over K
-                        Sp = ops.prefill_split_plan(M, *L0[k].shape)
-                        if Sp:
-                            plans[k] = (Sp, lambda a, w, S=Sp: ops.pgemm_partial(a, w, S))
-        if self.tp > 1 and not x.is_cuda:
-            # CPU TP rehearsal: row-parallel partials as fp32 slabs, all-reduced before the one
-            # bf16 rounding (comm.tp_add_rmsnorm), so TP = N tracks TP = 1's rounding
-            for k in ("o", "down"):
-                if not plans.get(k, (0, None))[0]:
-                    plans[k] = (1, lambda a, w: F.linear(a.float(), w.float())[None])
-        # batch 1 (<= ops.NORM_FUSE_ROWS rows, TP = 1): O / down with the residual add + RMSNorm
-        # in the projection's own last workgroup -- no add_rmsnorm_splitk launch
-        nf = {}
-        if decode and self.tp == 1 and self.layers and x.is_cuda and not w8:
-            L0 = self.layers[0]
-            for k in ("o", "down"):
-                S = ops.dgemm_norm_plan(M, *L0[k].shape)
-                if S:
-                    nf[k] = S
-            if nf and self._ntick is None:
-                self._ntick = torch.zeros(1, dtype=torch.int32, device=self.device)
-        sq, qkv_part = plans.get("qkv", (0, None))
-        so, o_part = plans.get("o", (0, None))
-        sd, down_part = plans.get("down", (0, None))
         cascade = decode and meta.shared_len is not None
+        # which kernel every projection runs (split 0 = library GEMM + plain consumer)
+        plan = self._step_plan(M, meta, x.is_cuda, kv8,
+                               fused_attn=(decode and not cascade and meta.block_tables is not None
+                                           and bool(kv_caches)
+                                           and ops.fused_decode_ok(kv_caches[0][0], meta.block_tables)))
+        sq, so, sd = plan.splits("qkv"), plan.splits("o"), plan.splits("down")
+        nf, xn = plan.nf, plan.xn
+        fmt = self.streamed.fmt if plan.streamed else ""
+        if nf and self._ntick is None:
+            self._ntick = torch.zeros(1, dtype=torch.int32, device=self.device)
         trim = (not decode and _PREFILL_TRIM and x.is_cuda and logits_index is not None and self.layers
                 and meta.block_tables is not None and meta.prefix_lens is not None
                 and logits_index.numel() == meta.block_tables.shape[0] and M > logits_index.numel())
-        # batch 1 (one row, TP = 1, skinny-kernel plans): the gate|up and the next layer's QKV
-        # projection build their input row themselves -- residual add + RMSNorm of the previous
-        # projection's slabs, in LDS, under their first weight stages (dgemm.hip XNormIn) --
-        # so no add_rmsnorm launch runs between projections; the residual ping-pongs between
-        # two buffers (one workgroup writes the new one while the others read the old)
-        xn = (decode and self.tp == 1 and not nf and x.is_cuda and sq and so and sd
-              and self.layers and ops.xn_ok(M, self.cfg.hidden)
-              and not ops.mid_plan(M, *self.layers[0]["gate_up"].shape, glu=True)[0])
         res2 = torch.empty_like(residual) if xn else None
         pd = None   # XN: the previous layer's down-projection slabs
         for i, L in enumerate(self.layers):
             kc, vc = kv_caches[i]
-            if w8:   # this layer's weights: the FP8 (q, s) / MXFP4 (q, e) pairs where the plan streams them
-                L = {**L, **{k: wq[i][k] for k in w8}}
+            if plan.streamed:   # this layer's weights: the streamed pairs where the plan reads them
+                L = {**L, **{k: self.streamed.layers[i][k] for k in plan.streamed}}
             if sq:
                 if xn and pd is not None:
                     Sg, R = ops.gemv_plan(M, *self.layers[i]["qkv"].shape)
-                    if "qkv" in w8 and use4:
-                        qkv_slabs = ops.gemv4_partial_xn(pd, residual, res2, L["in_norm"], eps, *L["qkv"], sq,
-                                                         w8["qkv"][1])
-                    elif "qkv" in w8:
-                        qkv_slabs = ops.gemv8_partial_xn(pd, residual, res2, L["in_norm"], eps, *L["qkv"], sq,
-                                                         w8["qkv"][1])
+                    if "qkv" in plan.streamed:
+                        qkv_slabs = ops.streamed_partial_xn(fmt, plan.streamed["qkv"], pd, residual, res2,
+                                                            L["in_norm"], eps, L["qkv"], sq, plan.proj["qkv"][2])
                     elif Sg == sq:
                         qkv_slabs = ops.gemv_partial_xn(pd, residual, res2, L["in_norm"], eps, L["qkv"], sq, R)
                     else:
                         qkv_slabs = ops.dgemm_partial_xn(pd, residual, res2, L["in_norm"], eps, L["qkv"], sq)
                     residual, res2 = res2, residual
                 else:
-                    qkv_slabs = qkv_part(x, L["qkv"])
+                    qkv_slabs = self._partial(plan.proj["qkv"], x, L["qkv"])
             if cascade:
                 # shared-prefix decode: RoPE + cache write, then prefix-once + suffix attention
                 if (sq and meta.decode_groups is not None and meta.decode_inline and x.is_cuda
@@ -654,16 +661,16 @@ class LlamaModel:
                                      meta.max_context, self.scale, meta.seq_order)
             nxt = self.layers[i + 1]["in_norm"] if i + 1 < nl else self.final_norm
             if xn:
-                if "gate_up" in w8 and use4:
-                    g = ops.gemv4_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, *L["gate_up"])
-                elif "gate_up" in w8:
-                    g = ops.gemv8_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, *L["gate_up"])
+                po = self._partial(plan.proj["o"], a, L["o"])
+                if "gate_up" in plan.streamed:
+                    g = ops.streamed_glu_xn(fmt, plan.streamed["gate_up"], po, residual, res2, L["post_norm"], eps,
+                                            L["gate_up"])
                 elif ops.gemv_glu_ok(M, *L["gate_up"].shape):
-                    g = ops.gemv_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, L["gate_up"])
+                    g = ops.gemv_glu_xn(po, residual, res2, L["post_norm"], eps, L["gate_up"])
                 else:
-                    g = ops.dgemm_glu_xn(o_part(a, L["o"]), residual, res2, L["post_norm"], eps, L["gate_up"])
+                    g = ops.dgemm_glu_xn(po, residual, res2, L["post_norm"], eps, L["gate_up"])
                 residual, res2 = res2, residual
-                pd = down_part(g, L["down"])
+                pd = self._partial(plan.proj["down"], g, L["down"])
                 if i + 1 == nl:
                     x = ops.add_rmsnorm_splitk(pd, residual, nxt, eps)
                 continue
@@ -671,12 +678,14 @@ class LlamaModel:
             if "o" in nf:
                 x = ops.dgemm_add_rmsnorm(a, L["o"], nf["o"], residual, L["post_norm"], eps, self._ntick)
             else:
-                x = comm.tp_add_rmsnorm(o_part(a, L["o"]) if so else lin(a, L["o"]), residual, L["post_norm"], eps)
-            g = glu(x, L["gate_up"])
+                x = comm.tp_add_rmsnorm(self._partial(plan.proj["o"], a, L["o"]) if so else lin(a, L["o"]),
+                                        residual, L["post_norm"], eps)
+            g = self._glu(plan, x, L["gate_up"])
             if "down" in nf:
                 x = ops.dgemm_add_rmsnorm(g, L["down"], nf["down"], residual, nxt, eps, self._ntick)
             else:
-                x = comm.tp_add_rmsnorm(down_part(g, L["down"]) if sd else lin(g, L["down"]), residual, nxt, eps)
+                x = comm.tp_add_rmsnorm(self._partial(plan.proj["down"], g, L["down"]) if sd else lin(g, L["down"]),
+                                        residual, nxt, eps)
         if logits_index is not None:
             x = x.index_select(0, logits_index)
         if greedy_ids:
@@ -769,8 +778,9 @@ class LlamaModel:
                                                    and ops.lm_head_argmax_shape_ok(N, K))
         if self.tp == 1:
             if fused:
-                return ops.lm_head_argmax(x, self.lm_head, self.cfg.vocab_size, fp8=self.lm_head_fp8,
-                                          mxfp4=self.lm_head_mx4)
+                s = self.streamed
+                return ops.lm_head_argmax(x, self.lm_head, self.cfg.vocab_size,
+                                          streamed=(s.fmt, s.lm_head) if s is not None else None)
             return self.greedy(ops.lm_head_logits(x, self.lm_head))
         if fused and self.vocab_valid > 0:
             ids, vals = ops.lm_head_argmax(x, self.lm_head, self.vocab_valid, with_values=True)

@@ -12,6 +12,7 @@ from __future__ import annotations
 import os
 import threading
 from pathlib import Path
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -540,34 +541,29 @@ _LM_CFG = int(os.environ.get("DOCQA_LM_HEAD_CFG", "6"))
 _GEMV_LM = os.environ.get("DOCQA_GEMV_LM", "1") != "0"
 
 
-def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False, fp8=None, mxfp4=None):
+def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False, streamed=None, fp8=None,
+                   mxfp4=None):
     """Greedy token ids argmax(bf16(x @ w[:n_valid]^T)) with the LM-head GEMM and the argmax
     fused (mgemm.hip EPI_ARGMAX): the [M, vocab] logits never reach HBM.  ``with_values``:
     (ids, picked logit fp32) -- a vocab-parallel shard's candidates for comm.tp_argmax.
-    ``fp8``: the (q, s) FP8 copy of ``w`` (:func:`quantize_fp8_rows`, ``w`` its exact image) --
-    a one-row step then streams the codes (dgemm.hip gemv8_kernel EPI_ARGMAX), a 2..32-row
-    step too where :func:`dgemm8_argmax_ok` (dgemm8_kernel EPI_ARGMAX).
-    ``mxfp4``: the (q, e) MXFP4 copy of ``w`` (:func:`quantize_mxfp4_rows`, ``w`` its exact
-    image) -- a one-row step streams the codes where :func:`gemv4_argmax_ok` (gemv4_kernel
-    EPI_ARGMAX), a 2..32-row step where :func:`dgemm4_argmax_ok` (dgemm4_kernel EPI_ARGMAX); every
-    other step runs on ``w``."""
+    ``streamed``: (format, pair), a :data:`STREAMED` copy of ``w`` (``w`` its exact image): (q, s)
+    of :func:`quantize_fp8_rows` or (q, e) of :func:`quantize_mxfp4_rows` -- a one-row step
+    streams the codes where the format's GEMV lists the shape, a 2..32-row step where its ring
+    kernel does (dgemm.hip EPI_ARGMAX); every other step runs on ``w``.  ``fp8=pair`` and
+    ``mxfp4=pair`` spell the same argument per format."""
+    if streamed is None and (fp8 is not None or mxfp4 is not None):
+        streamed = ("mxfp4", mxfp4) if mxfp4 is not None else ("fp8-e4m3", fp8)
     if _gpu(x):
         N, K = w.shape
-        if mxfp4 is not None and n_valid > 0 and gemv4_argmax_ok(x.numel() // K, N, K):
-            R, lb, kw = _GEMV4_EPI[K]
-            ids, vals = _native().gemv4_argmax_val(x.contiguous(), mxfp4[0], mxfp4[1], int(n_valid), R, lb, kw)
-            return (ids, vals) if with_values else ids
-        if mxfp4 is not None and n_valid > 0 and dgemm4_argmax_ok(x.numel() // K, N, K):
-            # 2..32 rows: the ring kernel over the codes (dgemm.hip dgemm4_kernel EPI_ARGMAX)
-            ids, vals = _native().dgemm4_argmax_val(x.contiguous(), mxfp4[0], mxfp4[1], int(n_valid))
-            return (ids, vals) if with_values else ids
-        if fp8 is not None and n_valid > 0 and gemv8_argmax_ok(x.numel() // K, N, K):
-            R, lb = _GEMV8_EPI[K]
-            ids, vals = _native().gemv8_argmax_val(x.contiguous(), fp8[0], fp8[1], int(n_valid), R, lb)
-            return (ids, vals) if with_values else ids
-        if fp8 is not None and n_valid > 0 and dgemm8_argmax_ok(x.numel() // K, N, K):
-            # 2..32 rows: the ring kernel over the codes (dgemm.hip dgemm8_kernel EPI_ARGMAX)
-            ids, vals = _native().dgemm8_argmax_val(x.contiguous(), fp8[0], fp8[1], int(n_valid))
+        fmt, pair = streamed or ("", None)
+        kind = next((k for k in _KINDS if fmt and n_valid > 0
+                     and _streamed_fn(fmt, k, "argmax_ok")(x.numel() // K, N, K)), "")
+        if kind:
+            # the GEMV takes its (rows, codes per load ...) from the format's EPI table
+            f = STREAMED[fmt]
+            epi = globals()[f.gemv_epi][K] if kind == "gemv" else ()
+            op = getattr(_native(), f"{getattr(f, kind)}_argmax_val")
+            ids, vals = op(x.contiguous(), *pair, int(n_valid), *epi)
             return (ids, vals) if with_values else ids
         if (_GEMV_LM and x.numel() == K and N % 16 == 0 and K % 2048 == 0 and K // 2048 <= 2
                 and n_valid > 0):
@@ -936,21 +932,33 @@ _DGEMM8_GLU: dict = {(28672, 4096): _B8, (16384, 2048): _B8}
 _DGEMM8_LM: dict = {(128256, 4096): _B8, (32768, 4096): _B8, (32000, 2048): _B8}
 
 
-def _dgemm8_listed(table: dict, M: int, N: int, K: int) -> bool:
-    if not _DGEMM8 or not (2 <= M <= DGEMM8_MAX_ROWS) or N % 64 or K % DGEMM8_K:
+def _ring_listed(on: bool, max_rows: int, granule: int, table: dict, M: int, N: int, K: int) -> bool:
+    """A ring kernel's plan table lists this shape at this step's bucket."""
+    if not on or not (2 <= M <= max_rows) or N % 64 or K % granule:
         return False
     return (1 << (M - 1).bit_length()) in table.get((N, K), ())
+
+
+def _ring_splits(N: int, K: int, granule: int, tile: int, min_wgs: int) -> int:
+    """:func:`decode_plan`'s split rule on a ring kernel's K granule: the smallest S (slices of
+    whole ``granule``-deep ring turns) giving >= ``min_wgs`` workgroups, else the most slices there
+    are; 0 where K is not whole ring turns."""
+    if N % tile or K % granule or K < granule:
+        return 0
+    turns = K // granule
+    cands = [S for S in range(1, turns + 1) if turns % S == 0]
+    return next((S for S in cands if (N // tile) * S >= min_wgs), cands[-1])
+
+
+def _dgemm8_listed(table: dict, M: int, N: int, K: int) -> bool:
+    return _ring_listed(_DGEMM8, DGEMM8_MAX_ROWS, DGEMM8_K, table, M, N, K)
 
 
 def dgemm8_splits(N: int, K: int, tile: int = 64, min_wgs: int = 192) -> int:
     """:func:`decode_plan`'s split rule on the FP8 ring's K granule: the smallest S (slices of
     whole 1024-deep ring turns) giving >= ``min_wgs`` workgroups, else the most slices there
     are; 0 where K is not whole ring turns."""
-    if N % tile or K % DGEMM8_K or K < DGEMM8_K:
-        return 0
-    turns = K // DGEMM8_K
-    cands = [S for S in range(1, turns + 1) if turns % S == 0]
-    return next((S for S in cands if (N // tile) * S >= min_wgs), cands[-1])
+    return _ring_splits(N, K, DGEMM8_K, tile, min_wgs)
 
 
 def dgemm8_plan(M: int, N: int, K: int) -> tuple[int, int]:
@@ -1026,20 +1034,14 @@ _DGEMM4_LM: dict = {(128256, 4096): _B4, (32768, 4096): _B4, (32000, 2048): _B4}
 
 
 def _dgemm4_listed(table: dict, M: int, N: int, K: int) -> bool:
-    if not _DGEMM4 or not (2 <= M <= DGEMM4_MAX_ROWS) or N % 64 or K % DGEMM4_K:
-        return False
-    return (1 << (M - 1).bit_length()) in table.get((N, K), ())
+    return _ring_listed(_DGEMM4, DGEMM4_MAX_ROWS, DGEMM4_K, table, M, N, K)
 
 
 def dgemm4_splits(N: int, K: int, tile: int = 64, min_wgs: int = 192) -> int:
     """:func:`dgemm8_splits` on the MXFP4 ring's K granule: the smallest S (slices of whole
     2048-deep ring turns) giving >= ``min_wgs`` workgroups, else the most slices there are; 0
     where K is not whole ring turns."""
-    if N % tile or K % DGEMM4_K or K < DGEMM4_K:
-        return 0
-    turns = K // DGEMM4_K
-    cands = [S for S in range(1, turns + 1) if turns % S == 0]
-    return next((S for S in cands if (N // tile) * S >= min_wgs), cands[-1])
+    return _ring_splits(N, K, DGEMM4_K, tile, min_wgs)
 
 
 def dgemm4_plan(M: int, N: int, K: int) -> tuple[int, int]:
@@ -1077,6 +1079,68 @@ def dgemm4_glu(x, q, e):
     if _gpu(x):
         return _native().dgemm4_glu(x.contiguous(), q, e)
     return glu_linear(x, dequantize_mxfp4_rows(q, e, x.dtype))
+
+
+# ----------------------------------------------------------------- streamed-weight dispatch
+class StreamedFormat(NamedTuple):
+    """One streamed weight format: a quantized copy (a pair of tensors per weight) next to its exact
+    bf16 image W', read by a one-row GEMV and a 2..max_rows-row ring kernel.  Every per-format
+    function is named <kernel family>_<role> (gemv8_plan, dgemm4_glu_ok, gemv4_partial_xn ...) and
+    looked up on this module when called: tests spy on the wrappers and patch the plan tables."""
+    quantize: Callable
+    dequantize: Callable
+    max_rows: int
+    gemv: str          # kernel family of one-row steps
+    ring: str          # kernel family of 2..max_rows-row steps
+    gemv_epi: str      # table K -> launch arguments of the GEMV's SwiGLU / argmax epilogues
+
+
+STREAMED = {"fp8-e4m3": StreamedFormat(quantize_fp8_rows, dequantize_fp8_rows, DGEMM8_MAX_ROWS,
+                                       "gemv8", "dgemm8", "_GEMV8_EPI"),
+            "mxfp4": StreamedFormat(quantize_mxfp4_rows, dequantize_mxfp4_rows, DGEMM4_MAX_ROWS,
+                                    "gemv4", "dgemm4", "_GEMV4_EPI")}
+_KINDS = ("gemv", "ring")      # the order they are tried in
+
+
+def _streamed_fn(fmt: str, kind: str, role: str):
+    return globals()[f"{getattr(STREAMED[fmt], kind)}_{role}"]
+
+
+def streamed_plan(fmt: str, M: int, N: int, K: int) -> tuple[str, int, int]:
+    """(kind, split-K count, weight rows per workgroup) of an M-row slab projection over the
+    streamed copy, kind "gemv" or "ring"; ("", 0, 0) where neither plan lists the shape (the
+    caller then streams the bf16 image W')."""
+    for kind in _KINDS:
+        S, R = _streamed_fn(fmt, kind, "plan")(M, N, K)
+        if S:
+            return kind, S, R
+    return "", 0, 0
+
+
+def streamed_glu_kind(fmt: str, M: int, N: int, K: int) -> str:
+    """:func:`streamed_plan`'s kind for the gate|up projection with SwiGLU."""
+    return next((kind for kind in _KINDS if _streamed_fn(fmt, kind, "glu_ok")(M, N, K)), "")
+
+
+def streamed_partial(fmt: str, kind: str, x, w, splits: int, rows: int):
+    """fp32 slabs [S, M, N] of x @ W'^T from the streamed pair ``w`` (:func:`streamed_plan`)."""
+    return _streamed_fn(fmt, kind, "partial")(x, *w, splits, rows)
+
+
+def streamed_partial_xn(fmt: str, kind: str, Pin, res_in, res_out, gamma, eps: float, w, splits: int, rows: int):
+    """:func:`streamed_partial` with the input row built in-kernel (:func:`gemv_partial_xn`)."""
+    return _streamed_fn(fmt, kind, "partial_xn")(Pin, res_in, res_out, gamma, eps, *w, splits, rows)
+
+
+def streamed_glu(fmt: str, kind: str, x, w):
+    """silu(x Wg^T) * (x Wu^T) from the streamed pair ``w`` (:func:`streamed_glu_kind`)."""
+    return _streamed_fn(fmt, kind, "glu")(x, *w)
+
+
+def streamed_glu_xn(fmt: str, kind: str, Pin, res_in, res_out, gamma, eps: float, w):
+    """:func:`streamed_glu` with the input row built in-kernel (:func:`gemv_glu_xn`)."""
+    return _streamed_fn(fmt, kind, "glu_xn")(Pin, res_in, res_out, gamma, eps, *w)
+
 
 
 NORM_FUSE_ROWS = 4
