@@ -1213,6 +1213,54 @@ std::tuple<at::Tensor, at::Tensor> dgemm8_argmax_val(const at::Tensor& x, const 
   return {out, outv};
 }
 
+// 33..128-row decode projections over FP8 weights (dgemm.hip dgemm8w_kernel); the row range is the
+// entry point's check: a shape without an instantiation launches nothing and raises, naming the op
+static int dgemm8w_rows(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, const char* op) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(), op,
+              ": x must be a contiguous bfloat16 GPU tensor");
+  check_fp8w(q, scale, op);
+  const int64_t K = x.size(-1);
+  TORCH_CHECK(K > 0 && q.size(1) == K, op, ": K mismatch");
+  return (int)std::min<int64_t>(x.numel() / K, 1 << 20);
+}
+
+at::Tensor dgemm8w_partial(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale, int64_t splits,
+                           int64_t tile_rows) {
+  const int M = dgemm8w_rows(x, q, scale, "dgemm8w_partial");
+  const int N = q.size(0), K = q.size(1);
+  TORCH_CHECK(splits >= 1 && splits <= 64, "dgemm8w_partial: splits in 1..64");
+  c10::DeviceGuard g(x.device());
+  auto part = at::empty({splits, M, N}, x.options().dtype(at::kFloat));
+  CHECK_RC(docqa_dgemm8w_partial(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), part.data_ptr<float>(), M, N, K,
+                                 (int)splits, (int)tile_rows, stream()), "dgemm8w_partial");
+  return part;
+}
+
+at::Tensor dgemm8w_glu(const at::Tensor& x, const at::Tensor& q, const at::Tensor& scale) {
+  const int M = dgemm8w_rows(x, q, scale, "dgemm8w_glu");
+  const int N = q.size(0), K = q.size(1);
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({M, N / 2}, x.options());
+  CHECK_RC(docqa_dgemm8w_glu(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), M, N, K, stream()),
+           "dgemm8w_glu");
+  return out;
+}
+
+std::tuple<at::Tensor, at::Tensor> dgemm8w_argmax_val(const at::Tensor& x, const at::Tensor& q,
+                                                      const at::Tensor& scale, int64_t n_valid) {
+  const int M = dgemm8w_rows(x, q, scale, "dgemm8w_argmax_val");
+  const int N = q.size(0), K = q.size(1);
+  c10::DeviceGuard g(x.device());
+  auto out = at::empty({M}, x.options().dtype(at::kLong));
+  auto outv = at::empty({M}, x.options().dtype(at::kFloat));
+  auto ws_v = at::empty({M, N / 128 + 1}, x.options().dtype(at::kFloat));
+  auto ws_i = at::empty({M, N / 128 + 1}, x.options().dtype(at::kInt));
+  CHECK_RC(docqa_dgemm8w_argmax(x.data_ptr(), q.data_ptr(), scale.data_ptr<float>(), out.data_ptr<int64_t>(),
+                                outv.data_ptr<float>(), ws_v.data_ptr<float>(), ws_i.data_ptr<int>(), M, N, K,
+                                (int)n_valid, stream()), "dgemm8w_argmax_val");
+  return {out, outv};
+}
+
 // 2..32-row decode projections over MXFP4 weights (dgemm.hip dgemm4_kernel); a shape without an
 // instantiation launches nothing and raises, naming the op
 static int dgemm4_rows(const at::Tensor& x, const at::Tensor& q, const at::Tensor& e, const char* op, int* K) {
@@ -1812,6 +1860,9 @@ TORCH_LIBRARY(docqa, m) {
   m.def("dgemm8_partial(Tensor x, Tensor q, Tensor scale, int splits, int tile_rows=64) -> Tensor");
   m.def("dgemm8_glu(Tensor x, Tensor q, Tensor scale) -> Tensor");
   m.def("dgemm8_argmax_val(Tensor x, Tensor q, Tensor scale, int n_valid) -> (Tensor, Tensor)");
+  m.def("dgemm8w_partial(Tensor x, Tensor q, Tensor scale, int splits, int tile_rows=128) -> Tensor");
+  m.def("dgemm8w_glu(Tensor x, Tensor q, Tensor scale) -> Tensor");
+  m.def("dgemm8w_argmax_val(Tensor x, Tensor q, Tensor scale, int n_valid) -> (Tensor, Tensor)");
   m.def("dgemm4_partial(Tensor x, Tensor q, Tensor e, int splits, int tile_rows=64) -> Tensor");
   m.def("dgemm4_glu(Tensor x, Tensor q, Tensor e) -> Tensor");
   m.def("dgemm4_argmax_val(Tensor x, Tensor q, Tensor e, int n_valid) -> (Tensor, Tensor)");
@@ -1915,6 +1966,9 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("dgemm8_partial", &dgemm8_partial);
   m.impl("dgemm8_glu", &dgemm8_glu);
   m.impl("dgemm8_argmax_val", &dgemm8_argmax_val);
+  m.impl("dgemm8w_partial", &dgemm8w_partial);
+  m.impl("dgemm8w_glu", &dgemm8w_glu);
+  m.impl("dgemm8w_argmax_val", &dgemm8w_argmax_val);
   m.impl("dgemm4_partial", &dgemm4_partial);
   m.impl("dgemm4_glu", &dgemm4_glu);
   m.impl("dgemm4_argmax_val", &dgemm4_argmax_val);

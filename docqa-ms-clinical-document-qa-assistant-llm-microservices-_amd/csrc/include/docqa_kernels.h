@@ -205,6 +205,15 @@ int docqa_dgemm8_partial(const void* X, const void* Wq, const float* scale, floa
 int docqa_dgemm8_glu(const void* X, const void* Wq, const float* scale, void* Y, int M, int N, int K, hipStream_t s);
 int docqa_dgemm8_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
                         int* ws_i, int M, int N, int K, int n_valid, hipStream_t s);
+// 33..128-row decode projections over FP8 weights (dgemm.hip dgemm8w_kernel: waves own n-tiles of a
+// 128-row weight tile, X staged through LDS; K slices of whole 512-deep turns): outputs as
+// docqa_dgemm8_* (tile_rows 128; ws_v / ws_i: [M, N / 128]).  -1 (nothing launched) for M outside
+// 33..128, N % 128, a K slice that is not whole turns, pointers off 16 B, n_valid outside 1..N.
+int docqa_dgemm8w_partial(const void* X, const void* Wq, const float* scale, float* P, int M, int N, int K, int S,
+                          int tile_rows, hipStream_t s);
+int docqa_dgemm8w_glu(const void* X, const void* Wq, const float* scale, void* Y, int M, int N, int K, hipStream_t s);
+int docqa_dgemm8w_argmax(const void* X, const void* Wq, const float* scale, int64_t* out, float* outv, float* ws_v,
+                         int* ws_i, int M, int N, int K, int n_valid, hipStream_t s);
 // 2..32-row decode projections over MXFP4 weights (dgemm.hip dgemm4_kernel: the same ring over
 // Wq [N, K / 2] e2m1 code pairs and E [N, K / 32] e8m0 block scales, K slices of whole 2048-deep
 // ring turns): outputs as docqa_dgemm8_*; slab tiles of 64, 32 or 16 weight rows (tile_rows).  -1

@@ -155,7 +155,8 @@ class Streamed(NamedTuple):
 @dataclass
 class StepPlan:
     """Which kernel every projection of one forward runs (LlamaModel._step_plan): plain data.  The
-    families "streamed_gemv" / "streamed_ring" read the streamed pair (ops.streamed_plan's kinds);
+    families "streamed_gemv" / "streamed_ring" / "streamed_wide" read the streamed pair
+    (ops.streamed_plan's kinds);
     "gemv", "mgemm", "dgemm", "pgemm" (ops.<family>_partial) and "linear32" the bf16 weights."""
     # "qkv" | "o" | "down" -> (family, split-K count, rows | tile | cfg, bf16 slabs); absent or
     # split-K count 0: the library GEMM with the plain consumer
@@ -312,8 +313,9 @@ class LlamaModel:
     FP8_WEIGHTS = STREAMED_WEIGHTS      # the name the weight tests read
 
     def quantize_fp8(self) -> None:
-        """FP8 weight streaming for decode steps of 1..ops.DGEMM8_MAX_ROWS rows (TP = 1; one row:
-        the GEMV, 2..32 rows: the ring kernel, each where its plan lists the shape): every
+        """FP8 weight streaming for decode steps of 1..ops.DGEMM8W_MAX_ROWS rows (TP = 1; one row:
+        the GEMV, 2..32 rows: the ring kernel, 33..128 rows: the wide kernel whose waves own
+        n-tiles, each where its plan lists the shape): every
         projection and the LM head get a per-row e4m3fn copy (q, s) with power-of-two scales
         (ops.quantize_fp8_rows), and the resident weights are REPLACED by its exact image
         W' = q * s.  Every kernel that reads W' (prefill, batched decode, mixed steps, sampled
@@ -397,7 +399,7 @@ class LlamaModel:
         itself (ops.fused_decode_ok of the cache).  Decode steps stream every weight once: per
         projection a split-K kernel emits slabs straight into the fused consumers (RoPE + KV write
         for QKV, (TP all-reduce +) residual add + RMSNorm for O / down); steps of 1..max_rows rows
-        of a quantized model read its streamed copy where the format's plans list a kernel
+        (FP8: 128, MXFP4: 32) of a quantized model read its streamed copy where the format's plans list a kernel
         (ops.streamed_plan / streamed_glu_kind), everything else the bf16 image W'."""
         plan = StepPlan()
         decode = not meta.prefill
@@ -425,7 +427,7 @@ class LlamaModel:
                 N, K = shape[k]
                 kind, S, R = ops.streamed_plan(fmt, M, N, K) if fmt else ("", 0, 0)
                 if kind:
-                    # the GEMV or the ring kernel over the streamed pair
+                    # the GEMV, the ring kernel or the wide kernel over the streamed pair
                     plan.streamed[k] = kind
                     plan.proj[k] = ("streamed_" + kind, S, R, False)
                     continue

@@ -549,15 +549,16 @@ def lm_head_argmax(x, w, n_valid: int, cfg: int = -1, with_values: bool = False,
     ``streamed``: (format, pair), a :data:`STREAMED` copy of ``w`` (``w`` its exact image): (q, s)
     of :func:`quantize_fp8_rows` or (q, e) of :func:`quantize_mxfp4_rows` -- a one-row step
     streams the codes where the format's GEMV lists the shape, a 2..32-row step where its ring
-    kernel does (dgemm.hip EPI_ARGMAX); every other step runs on ``w``.  ``fp8=pair`` and
+    kernel does, a 33..128-row step where its wide kernel does (dgemm.hip EPI_ARGMAX); every other
+    step runs on ``w``.  ``fp8=pair`` and
     ``mxfp4=pair`` spell the same argument per format."""
     if streamed is None and (fp8 is not None or mxfp4 is not None):
         streamed = ("mxfp4", mxfp4) if mxfp4 is not None else ("fp8-e4m3", fp8)
     if _gpu(x):
         N, K = w.shape
         fmt, pair = streamed or ("", None)
-        kind = next((k for k in _KINDS if fmt and n_valid > 0
-                     and _streamed_fn(fmt, k, "argmax_ok")(x.numel() // K, N, K)), "")
+        kind = next((k for k in (_kinds(fmt) if fmt and n_valid > 0 else ())
+                     if _streamed_fn(fmt, k, "argmax_ok")(x.numel() // K, N, K)), "")
         if kind:
             # the GEMV takes its (rows, codes per load ...) from the format's EPI table
             f = STREAMED[fmt]
@@ -908,8 +909,8 @@ def gemv4_glu_xn(Pin, res_in, res_out, gamma, eps: float, q, e, rows: int = 0, l
 
 # 2..DGEMM8_MAX_ROWS-row decode steps over the same (q, s) copies (dgemm.hip dgemm8_kernel: the
 # skinny kernel's LDS-DMA ring filled with codes, 256 per weight row per stage -- K slices of
-# whole 1024-deep ring turns).  33+ rows stay on W': there every wave of the ring kernel would
-# widen every B fragment, four times redundantly, and no 4-m-tile variant is built.
+# whole 1024-deep ring turns).  33+ rows are not this kernel's: there every wave of it would widen
+# every B fragment, four times redundantly -- 33..128 rows have the dgemm8w family below.
 DGEMM8_MAX_ROWS = 32
 DGEMM8_K = 1024
 _DGEMM8 = os.environ.get("DOCQA_DGEMM8", "1") != "0"
@@ -995,10 +996,84 @@ def dgemm8_glu(x, q, s):
     return glu_linear(x, dequantize_fp8_rows(q, s, x.dtype))
 
 
+# 33..DGEMM8W_MAX_ROWS-row decode steps over the same (q, s) copies (dgemm.hip dgemm8w_kernel: waves
+# own the n-tiles of a 128-row weight tile, so a code is widened once per workgroup; X staged
+# through LDS next to the codes; K slices of whole 512-deep turns).  129+ rows stay on W'.
+DGEMM8W_MAX_ROWS = 128
+DGEMM8W_K = 512
+DGEMM8W_TILE = 128
+_DGEMM8W = os.environ.get("DOCQA_DGEMM8W", "1") != "0"
+# (N, K) -> decode buckets whose step takes the wide FP8 kernel: slab projections (bucket ->
+# (split-K count, weight rows per workgroup), as _DGEMM4_SLAB), the fused-SwiGLU gate|up, the LM
+# head + argmax.  A (shape, bucket) pair is listed only where benchmarks/bench_dgemm_fp8_wide.py
+# measured the FP8 median below the shipped bf16 plan's (decode_plan / mid_plan, the mid-M LM head +
+# argmax; a slab projection whose split count differs from bf16's timed together with its consumer)
+# with disjoint min..max window ranges, in BOTH runs of profiles/fp8_wide_dgemm_probe.log.  Served
+# model shapes only: the test presets' shapes are never listed (tests patch the tables).
+# Llama-3-8B / Mistral-7B at M = 64 / 128, FP8 vs bf16 us (second run): gate|up 30.7 / 46.4 vs 52.8 /
+# 61.6 (glu_linear), LM head 132.3 / 192.8 vs 256.0 / 262.2 (Mistral 40.4 / 55.5 vs 108.5 / 110.0; the
+# mid-M LM head + argmax), down at S = 7 with add_rmsnorm_splitk 24.8 / 36.1 vs 31.7 / 46.0 (bf16: S = 4,
+# 64-row tiles; alone 18.4 / 30.9 vs 26.7 / 39.8), QKV at S = 4: bucket 64 with rope_cache_splitk 17.6 vs
+# 20.1 (bf16: S = 2), bucket 128 alone 20.5 vs 22.4 (bf16: S = 4 too).  65..128 rows (eight m-tiles
+# per B fragment, a 3-slot ring) are the slower instantiation: 43.2 us at 65 rows against 30.7 at 64 for
+# gate|up -- still ahead of bf16 everywhere listed.
+# Loser, which stays on W': O 4096 x 4096 at both buckets -- 32 tiles of 128 rows need S = 8 to fill
+# the chip, and the consumer then reads twice the slabs: 17.3 / 25.4 us with add_rmsnorm_splitk vs 16.3 /
+# 22.7; at bf16's own S = 4 alone 12.1 / 19.2 vs 12.0 / 16.8.
+_DGEMM8W_SLAB: dict = {(6144, 4096): {64: (4, 128), 128: (4, 128)},
+                       (4096, 14336): {64: (7, 128), 128: (7, 128)}}
+_DGEMM8W_GLU: dict = {(28672, 4096): (64, 128)}
+_DGEMM8W_LM: dict = {(128256, 4096): (64, 128), (32768, 4096): (64, 128)}
+
+
+def _dgemm8w_listed(table: dict, M: int, N: int, K: int) -> bool:
+    if not _DGEMM8W or not (DGEMM8_MAX_ROWS < M <= DGEMM8W_MAX_ROWS) or N % DGEMM8W_TILE or K % DGEMM8W_K:
+        return False
+    return (1 << (M - 1).bit_length()) in table.get((N, K), ())
+
+
+def dgemm8w_plan(M: int, N: int, K: int) -> tuple[int, int]:
+    """(split-K count, weight rows per workgroup) of the wide FP8-weight kernel for a 33..128-row
+    decode projection; (0, 128) where the shape has no instantiation, the table's split does not
+    cut K into whole 512-deep turns, or the probe did not show it faster than the bf16 plan (the
+    caller then streams W').  DOCQA_DGEMM8W=0 disables."""
+    if not _dgemm8w_listed(_DGEMM8W_SLAB, M, N, K):
+        return 0, DGEMM8W_TILE
+    S, t = _DGEMM8W_SLAB[(N, K)][1 << (M - 1).bit_length()]
+    if S < 1 or t != DGEMM8W_TILE or K % S or (K // S) % DGEMM8W_K:
+        return 0, DGEMM8W_TILE
+    return S, t
+
+
+def dgemm8w_glu_ok(M: int, N: int, K: int) -> bool:
+    """The 33..128-row gate|up projection with SwiGLU on the wide FP8-weight kernel."""
+    return _dgemm8w_listed(_DGEMM8W_GLU, M, N, K)
+
+
+def dgemm8w_argmax_ok(M: int, N: int, K: int) -> bool:
+    """The 33..128-row LM head + greedy pick on the wide FP8-weight kernel."""
+    return _dgemm8w_listed(_DGEMM8W_LM, M, N, K)
+
+
+def dgemm8w_partial(x, q, s, splits: int, tile_rows: int = DGEMM8W_TILE):
+    """fp32 slabs [S, M, N] of x @ (q * s)^T for 33..128 rows on the wide FP8-weight kernel
+    (:func:`dgemm8w_plan`)."""
+    if _gpu(x):
+        return _native().dgemm8w_partial(x.contiguous(), q, s, int(splits), int(tile_rows))
+    return dgemm_partial(x, dequantize_fp8_rows(q, s, x.dtype), splits, tile_rows)
+
+
+def dgemm8w_glu(x, q, s):
+    """silu(x Wg^T) * (x Wu^T) for 33..128 rows over FP8 8-interleaved gate|up weights."""
+    if _gpu(x):
+        return _native().dgemm8w_glu(x.contiguous(), q, s)
+    return glu_linear(x, dequantize_fp8_rows(q, s, x.dtype))
+
+
 # 2..DGEMM4_MAX_ROWS-row decode steps over the MXFP4 (q, e) copies (dgemm.hip dgemm4_kernel: the
 # same ring, 512 codes per weight row per stage -- K slices of whole 2048-deep ring turns, block
-# scales applied while widening; slab tiles of 64, 32 or 16 weight rows).  33+ rows stay on W', as
-# with FP8.
+# scales applied while widening; slab tiles of 64, 32 or 16 weight rows).  33+ rows stay on W':
+# the wide kernel (dgemm8w) is FP8 only.
 DGEMM4_MAX_ROWS = 32
 DGEMM4_K = 2048
 _DGEMM4 = os.environ.get("DOCQA_DGEMM4", "1") != "0"
@@ -1084,22 +1159,29 @@ def dgemm4_glu(x, q, e):
 # ----------------------------------------------------------------- streamed-weight dispatch
 class StreamedFormat(NamedTuple):
     """One streamed weight format: a quantized copy (a pair of tensors per weight) next to its exact
-    bf16 image W', read by a one-row GEMV and a 2..max_rows-row ring kernel.  Every per-format
+    bf16 image W', read by a one-row GEMV, a 2..32-row ring kernel and, where the format has one,
+    a wide kernel for the rows above (max_rows: the most rows any of them takes).  Every per-format
     function is named <kernel family>_<role> (gemv8_plan, dgemm4_glu_ok, gemv4_partial_xn ...) and
     looked up on this module when called: tests spy on the wrappers and patch the plan tables."""
     quantize: Callable
     dequantize: Callable
     max_rows: int
     gemv: str          # kernel family of one-row steps
-    ring: str          # kernel family of 2..max_rows-row steps
+    ring: str          # kernel family of 2..32-row steps
     gemv_epi: str      # table K -> launch arguments of the GEMV's SwiGLU / argmax epilogues
+    wide: str = ""     # kernel family of the steps above the ring kernel's rows; "": none
 
 
-STREAMED = {"fp8-e4m3": StreamedFormat(quantize_fp8_rows, dequantize_fp8_rows, DGEMM8_MAX_ROWS,
-                                       "gemv8", "dgemm8", "_GEMV8_EPI"),
+STREAMED = {"fp8-e4m3": StreamedFormat(quantize_fp8_rows, dequantize_fp8_rows, DGEMM8W_MAX_ROWS,
+                                       "gemv8", "dgemm8", "_GEMV8_EPI", "dgemm8w"),
             "mxfp4": StreamedFormat(quantize_mxfp4_rows, dequantize_mxfp4_rows, DGEMM4_MAX_ROWS,
                                     "gemv4", "dgemm4", "_GEMV4_EPI")}
-_KINDS = ("gemv", "ring")      # the order they are tried in
+_KINDS = ("gemv", "ring", "wide")      # the order they are tried in
+
+
+def _kinds(fmt: str) -> tuple:
+    """The kernel kinds format ``fmt`` has, in the order they are tried."""
+    return tuple(k for k in _KINDS if getattr(STREAMED[fmt], k))
 
 
 def _streamed_fn(fmt: str, kind: str, role: str):
@@ -1108,9 +1190,9 @@ def _streamed_fn(fmt: str, kind: str, role: str):
 
 def streamed_plan(fmt: str, M: int, N: int, K: int) -> tuple[str, int, int]:
     """(kind, split-K count, weight rows per workgroup) of an M-row slab projection over the
-    streamed copy, kind "gemv" or "ring"; ("", 0, 0) where neither plan lists the shape (the
+    streamed copy, kind "gemv", "ring" or "wide"; ("", 0, 0) where no plan lists the shape (the
     caller then streams the bf16 image W')."""
-    for kind in _KINDS:
+    for kind in _kinds(fmt):
         S, R = _streamed_fn(fmt, kind, "plan")(M, N, K)
         if S:
             return kind, S, R
@@ -1119,7 +1201,7 @@ def streamed_plan(fmt: str, M: int, N: int, K: int) -> tuple[str, int, int]:
 
 def streamed_glu_kind(fmt: str, M: int, N: int, K: int) -> str:
     """:func:`streamed_plan`'s kind for the gate|up projection with SwiGLU."""
-    return next((kind for kind in _KINDS if _streamed_fn(fmt, kind, "glu_ok")(M, N, K)), "")
+    return next((kind for kind in _kinds(fmt) if _streamed_fn(fmt, kind, "glu_ok")(M, N, K)), "")
 
 
 def streamed_partial(fmt: str, kind: str, x, w, splits: int, rows: int):
