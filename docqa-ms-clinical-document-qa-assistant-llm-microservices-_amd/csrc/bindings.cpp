@@ -495,6 +495,56 @@ at::Tensor penalized_argmax(at::Tensor logits, int64_t n_valid, const at::Tensor
   return out;
 }
 
+// ---- per-token log-probabilities -----------------------------------------------------------
+// logits [R, >= n_valid] bf16 / fp32 (row stride a multiple of 16 bytes; bf16: n_valid % 8 == 0),
+// chosen [R] int64, top_n [R] int32 (-1: skip the row, 0: the chosen logprob only, 1..20: also
+// that many alternatives) -> in place lp [R] fp32, top_ids [R, 20] int32, top_lp [R, 20] fp32.
+// The outputs are the caller's (a decode graph's static slot buffers); only the split
+// workspaces come from the caching allocator, like every other op's under capture.
+int64_t top_logprobs_max() { return docqa_top_logprobs_max(); }
+
+void token_logprobs(const at::Tensor& logits, int64_t n_valid, const at::Tensor& chosen, const at::Tensor& top_n,
+                    at::Tensor lp, at::Tensor top_ids, at::Tensor top_lp) {
+  CHECK_GPU(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "token_logprobs wants [rows, V] with unit stride");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "token_logprobs: bf16 or fp32 logits");
+  const int64_t R = logits.size(0), V = logits.size(1), ld = logits.stride(0);
+  const int64_t T = docqa_top_logprobs_max();
+  TORCH_CHECK(n_valid >= 1 && n_valid <= V, "token_logprobs: n_valid must be in [1, V]");
+  TORCH_CHECK(R <= 1 || ld >= V, "token_logprobs: row stride below V");
+  TORCH_CHECK(ld % (bf ? 8 : 4) == 0, "token_logprobs: row stride must be a multiple of 16 bytes");
+  TORCH_CHECK(!bf || n_valid % 8 == 0, "token_logprobs: bf16 logits need n_valid % 8 == 0");
+  CHECK_ALIGN16(logits);
+  const auto on_dev = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == logits.device(); };
+  TORCH_CHECK(on_dev(chosen) && on_dev(top_n) && on_dev(lp) && on_dev(top_ids) && on_dev(top_lp),
+              "token_logprobs: every tensor on the logits' device");
+  TORCH_CHECK(chosen.scalar_type() == at::kLong && chosen.numel() == R && chosen.is_contiguous(),
+              "token_logprobs: chosen must be contiguous int64 [rows]");
+  TORCH_CHECK(top_n.scalar_type() == at::kInt && top_n.numel() == R && top_n.is_contiguous(),
+              "token_logprobs: top_n must be contiguous int32 [rows]");
+  TORCH_CHECK(lp.scalar_type() == at::kFloat && lp.numel() == R && lp.is_contiguous(),
+              "token_logprobs: lp must be contiguous fp32 [rows]");
+  TORCH_CHECK(top_ids.scalar_type() == at::kInt && top_ids.dim() == 2 && top_ids.size(0) == R &&
+                  top_ids.size(1) == T && top_ids.is_contiguous(),
+              "token_logprobs: top_ids must be contiguous int32 [rows, TOP_LOGPROBS_MAX]");
+  TORCH_CHECK(top_lp.scalar_type() == at::kFloat && top_lp.dim() == 2 && top_lp.size(0) == R &&
+                  top_lp.size(1) == T && top_lp.is_contiguous(),
+              "token_logprobs: top_lp must be contiguous fp32 [rows, TOP_LOGPROBS_MAX]");
+  if (R == 0) return;
+  TORCH_CHECK(R <= 65535, "token_logprobs: at most 65535 rows");
+  const int splits = docqa_token_logprobs_splits((int)R, (int)n_valid, nullptr);
+  TORCH_CHECK(splits > 0, "token_logprobs: vocabulary too large for the split plan");
+  c10::DeviceGuard g(logits.device());
+  auto ws_f = at::empty({R * splits * (2 + T)}, logits.options().dtype(at::kFloat));
+  auto ws_i = at::empty({R * splits * T}, logits.options().dtype(at::kInt));
+  float* pm = ws_f.data_ptr<float>();
+  CHECK_RC(docqa_token_logprobs(logits.data_ptr(), (int)R, (int)n_valid, (int)ld, bf ? 1 : 0,
+                                chosen.data_ptr<int64_t>(), top_n.data_ptr<int>(), pm, pm + R * splits,
+                                pm + 2 * R * splits, ws_i.data_ptr<int>(), lp.data_ptr<float>(),
+                                top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), stream()), "token_logprobs");
+}
+
 // decode_advance + the ring: hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1 for valid rows
 void decode_advance_hist(const at::Tensor& nxt, at::Tensor out, at::Tensor tokens, at::Tensor positions,
                          at::Tensor context_lens, const at::Tensor& valid, at::Tensor hist,
@@ -1810,6 +1860,9 @@ TORCH_LIBRARY(docqa, m) {
         "Tensor pres_pen, Tensor freq_pen, Tensor? valid=None) -> ()");
   m.def("penalized_argmax(Tensor(a!) logits, int n_valid, Tensor hist, Tensor hist_n, Tensor last_n, "
         "Tensor rep_pen, Tensor pres_pen, Tensor freq_pen, Tensor? valid=None) -> Tensor");
+  m.def("top_logprobs_max() -> int", &top_logprobs_max);
+  m.def("token_logprobs(Tensor logits, int n_valid, Tensor chosen, Tensor top_n, Tensor(a!) lp, "
+        "Tensor(b!) top_ids, Tensor(c!) top_lp) -> ()");
   m.def("decode_advance_hist(Tensor nxt, Tensor(a!) out, Tensor(b!) tokens, Tensor(c!) positions, "
         "Tensor(d!) context_lens, Tensor valid, Tensor(e!) hist, Tensor(f!) hist_n) -> ()");
   m.def("paged_decode(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
@@ -1925,6 +1978,7 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("apply_penalties", &apply_penalties);
   m.impl("penalized_argmax", &penalized_argmax);
+  m.impl("token_logprobs", &token_logprobs);
   m.impl("decode_advance_hist", &decode_advance_hist);
   m.impl("paged_decode", &paged_decode);
   m.impl("flash_prefill", &flash_prefill);

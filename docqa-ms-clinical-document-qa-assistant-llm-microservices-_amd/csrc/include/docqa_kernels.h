@@ -83,6 +83,16 @@ int docqa_decode_advance_hist(const int64_t* nxt, int64_t* out, int* tokens, int
                               int* context_lens, const int* valid, int* hist, int W, int* hist_n,
                               int B, hipStream_t s);
 
+// per-token log-probabilities (logprobs.hip): lp[r] = logit[r, chosen[r]] - logsumexp(logit[r, :n_valid])
+// and the top_n[r] (<= docqa_top_logprobs_max()) most likely tokens; top_n[r] < 0 skips the row.
+// Workspaces: pm / ps >= rows * splits, ptv / pti >= rows * splits * docqa_top_logprobs_max(),
+// splits = docqa_token_logprobs_splits(rows, n_valid, nullptr) (0: vocabulary too large)
+int docqa_top_logprobs_max();
+int docqa_token_logprobs_splits(int rows, int V, int* chunk_out);
+int docqa_token_logprobs(const void* logits, int rows, int n_valid, int ld, int is_bf16, const int64_t* chosen,
+                         const int* top_n, float* pm, float* ps, float* ptv, int* pti, float* lp, int* top_ids,
+                         float* top_lp, hipStream_t s);
+
 int docqa_paged_decode(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                        const int* block_tables, int maxb, const int* context_lens, void* out,
                        int out_stride, float* tmp_out, float* tmp_ml, int B, int Hq, int Hkv,

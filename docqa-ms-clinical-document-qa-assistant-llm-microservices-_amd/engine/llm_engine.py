@@ -56,6 +56,14 @@ class SamplingParams:
     repeat_last_n: int = 64
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    # per-token log-probabilities of the model's distribution (the LM head's logits before
+    # penalties / temperature / top-k / top-p): the picked token's, and the ``top_logprobs``
+    # (0..ops.TOP_LOGPROBS_MAX, clamped) most likely tokens'
+    logprobs: bool = False
+    top_logprobs: int = 0
+
+    def __post_init__(self):
+        self.top_logprobs = max(0, min(int(self.top_logprobs), ops.TOP_LOGPROBS_MAX))
 
     @property
     def neutral(self) -> bool:
@@ -65,8 +73,14 @@ class SamplingParams:
 
     @property
     def fused_greedy_ok(self) -> bool:
-        """Greedy AND neutral: the LM head's fused argmax picks the token."""
-        return self.temperature <= 0.0 and self.neutral
+        """Greedy, neutral and no logprobs: the LM head's fused argmax picks the token (it
+        never writes the logits the logprobs are taken from)."""
+        return self.temperature <= 0.0 and self.neutral and not self.logprobs
+
+    @property
+    def lp_n(self) -> int:
+        """The request's ``top_n`` of :func:`ops.token_logprobs`: -1 without logprobs."""
+        return self.top_logprobs if self.logprobs else -1
 
 
 @dataclass
@@ -95,6 +109,11 @@ class Launched:
     t1: float
     # pinned copy of the TP all-reduce's error word behind the batch's kernels (None at TP 1)
     ar_err: torch.Tensor | None = None
+    # params.logprobs: host copies (pinned on a GPU) of every step's logprob buffers beside
+    # ``host`` -- lp [B, T] fp32, lp_top_ids [B, T, 20] int32, lp_top [B, T, 20] fp32; else None
+    lp: torch.Tensor | None = None
+    lp_top_ids: torch.Tensor | None = None
+    lp_top: torch.Tensor | None = None
 
     @property
     def done_event(self):
@@ -154,6 +173,13 @@ def ring_of(stream: list[int], W: int) -> tuple[torch.Tensor, int]:
         idx = torch.arange(n - m, n) % W
         row[idx] = torch.tensor(stream[n - m:], dtype=torch.int32)
     return row, n
+
+
+def logprob_entry(lp: float, top_ids: list[int], top_lp: list[float]) -> tuple:
+    """One token's ``(logprob, [(id, logprob), ...])`` from a row of the logprob buffers: the
+    top list ends at its first empty entry (id -1: past top_logprobs or past the vocabulary)."""
+    n = top_ids.index(-1) if -1 in top_ids else len(top_ids)
+    return float(lp), [(int(i), float(v)) for i, v in zip(top_ids[:n], top_lp[:n])]
 
 
 def _upload(dst: torch.Tensor, src: torch.Tensor) -> None:
@@ -267,6 +293,14 @@ class _DecodeGraph:
         self.pres_pen = torch.zeros(bp, dtype=torch.float32, device=dev)
         self.freq_pen = torch.zeros(bp, dtype=torch.float32, device=dev)
         self.penalized = False
+        # logprobs: what each slot asks of ops.token_logprobs (lp_n: -1 nothing, 0 the picked
+        # token's logprob, 1..20 also that many alternatives) and the step's results; only
+        # the logprob graphs touch them
+        self.lp_n = torch.full((bp,), -1, dtype=torch.int32, device=dev)
+        self.lp = torch.zeros(bp, dtype=torch.float32, device=dev)
+        self.lp_top_ids = torch.full((bp, ops.TOP_LOGPROBS_MAX), -1, dtype=torch.int32, device=dev)
+        self.lp_top = torch.full((bp, ops.TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=dev)
+        self.logprobs = False
         # cascade decode: block ids / length of the prompt prefix every row shares
         self.shared_table = torch.zeros(eng.max_blocks_per_seq, dtype=torch.int32, device=dev)
         self.shared_len = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -294,7 +328,8 @@ class _DecodeGraph:
         g = cls.__new__(cls)
         g.bp = bp
         for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
-                     "top_k", "top_p", "out", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen"):
+                     "top_k", "top_p", "out", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen",
+                     "lp_n", "lp", "lp_top_ids", "lp_top"):
             setattr(g, name, getattr(master, name)[:bp])
         g.shared_table, g.shared_len = master.shared_table, master.shared_len
         g.order = torch.arange(bp, dtype=torch.int32, device=master.tokens.device)
@@ -303,6 +338,7 @@ class _DecodeGraph:
         g.groups_key = None
         g.cascade, g.greedy, g.graph = False, True, None
         g.penalized = False
+        g.logprobs = False
         g.groups_fit = master.groups_fit
         g.hkv = master.hkv
         return g
@@ -484,6 +520,16 @@ class LLMEngine:
     # ------------------------------------------------------------------ decode step
     def _step_body(self, g: _DecodeGraph) -> None:
         meta = self._decode_meta(g)
+        if g.logprobs:
+            # logprob flavours: [B, vocab] logits, the slots' logprobs from them, and the pick
+            # the flavour has anyway (a greedy neutral row: the argmax of these very logits)
+            nxt = self._pick_logprobs(self.model.forward(g.tokens, meta, self.kv.caches), g)
+            if g.penalized:
+                ops.decode_advance_hist(nxt.long().contiguous(), g.out, g.tokens, g.positions, g.context_lens,
+                                        g.valid, g.hist, g.hist_n)
+            else:
+                ops.decode_advance(nxt.long().contiguous(), g.out, g.tokens, g.positions, g.context_lens, g.valid)
+            return
         if g.penalized:
             # penalised flavours: [B, vocab] logits, the pick under the slots' penalties, and
             # the new token joins each slot's ring inside the step
@@ -524,14 +570,17 @@ class LLMEngine:
                 meta.shared_table = meta.shared_len = meta.decode_groups = None
         return meta
 
-    def _select(self, logits, g: _DecodeGraph):
+    def _select(self, logits, g: _DecodeGraph, full=None):
+        """``full``: the logits already gathered over the vocab (:meth:`_pick_logprobs`); left
+        unchanged like ``logits``."""
         from .. import ops
 
         if g.greedy:
             return self.model.greedy(logits)
-        full = self.model.full_logits(logits).float()
+        src = self.model.full_logits(logits) if full is None else full
+        full = src.float()
         if g.penalized:
-            if not full.is_contiguous() or full.data_ptr() == logits.data_ptr():
+            if not full.is_contiguous() or full.data_ptr() in (logits.data_ptr(), src.data_ptr()):
                 full = full.clone(memory_format=torch.contiguous_format)   # never the caller's logits
             R = full.shape[0]   # the first-token pick covers the batch's rows, a step the bucket's
             ops.apply_penalties(full, g.hist[:R], g.hist_n[:R], g.last_n[:R], g.rep_pen[:R], g.pres_pen[:R],
@@ -539,24 +588,44 @@ class LLMEngine:
         u = torch.rand(full.shape[0], device=full.device)
         return ops.sample(full, g.inv_temp, g.top_k, g.top_p, u)
 
-    def _penalized_greedy(self, logits, g: _DecodeGraph):
+    def _penalized_greedy(self, logits, g: _DecodeGraph, full=None):
         """Greedy ids under the slots' penalties from the LM head's logits (gathered over the
-        vocab at TP > 1): one pass over the [R, vocab] logits, no fp32 copy, no sampler.
-        ``logits`` is clobbered."""
-        full = self.model.full_logits(logits)
+        vocab at TP > 1, or ``full``: already gathered): one pass over the [R, vocab] logits, no
+        fp32 copy, no sampler.  ``logits`` (``full``) is clobbered."""
+        full = self.model.full_logits(logits) if full is None else full
         R = full.shape[0]
         return ops.penalized_argmax(full, full.shape[1], g.hist[:R], g.hist_n[:R], g.last_n[:R], g.rep_pen[:R],
                                     g.pres_pen[:R], g.freq_pen[:R], g.valid[:R])
 
+    def _pick_logprobs(self, logits, g: _DecodeGraph):
+        """The flavour's pick from ``logits`` (the LM head's, a vocab shard at TP > 1) AND the
+        rows' log-probabilities into the slot buffers g.lp / g.lp_top_ids / g.lp_top, taken from
+        the logits as the LM head wrote them (gathered over the vocab at TP > 1): the kernel
+        needs the picked id, so it runs behind the pick, and the one pick that clobbers its
+        input (:meth:`_penalized_greedy`) works on a copy -- the sampler makes its own.  The
+        vocabulary is gathered once, for the pick and the kernel."""
+        full = self.model.full_logits(logits)
+        if g.penalized and g.greedy:
+            nxt = self._penalized_greedy(logits, g, full=full.clone())
+        elif g.greedy:
+            nxt = self.model.greedy(logits)
+        else:
+            nxt = self._select(logits, g, full=full)
+        R = full.shape[0]   # the first-token pick covers the batch's rows, a step the bucket's
+        ops.token_logprobs(full, self.cfg.vocab_size, nxt.long().contiguous(), g.lp_n[:R], g.lp[:R],
+                           g.lp_top_ids[:R], g.lp_top[:R])
+        return nxt
+
     def _get_graph(self, bp: int, greedy: bool, cascade: bool = False, fit: bool = True,
-                   penalized: bool = False) -> _DecodeGraph:
+                   penalized: bool = False, logprobs: bool = False) -> _DecodeGraph:
         fit = fit or self.max_blocks_per_seq <= ops.GROUP_MAX_BLOCKS
-        key = (bp, greedy, cascade, fit, penalized)
+        key = (bp, greedy, cascade, fit, penalized, logprobs)
         g = self._graphs.get(key)
         if g is None:
             g = _DecodeGraph(self, bp)
             g.greedy = greedy
             g.penalized = penalized
+            g.logprobs = logprobs
             g.cascade = cascade
             g.groups_fit = fit
             self._graphs[key] = g
@@ -758,15 +827,17 @@ class LLMEngine:
         g.graph = graph
 
     @torch.inference_mode()
-    def warm_graphs(self, batch: int, greedy: bool = True, penalized: bool = False) -> None:
+    def warm_graphs(self, batch: int, greedy: bool = True, penalized: bool = False,
+                    logprobs: bool = False) -> None:
         """Capture the decode graphs (plain and cascade) of the bucket serving ``batch``
         sequences now, with empty slots (valid 0: nothing is written to the KV cache), so
-        the first batch that hits the cascade path does not pay a capture / GEMM tuning."""
+        the first batch that hits the cascade path does not pay a capture / GEMM tuning.
+        ``logprobs``: the flavour that also computes per-token log-probabilities."""
         if not self.use_graphs:
             return
         bp = _bucket(batch, self.max_batch)
         for cascade in ([False, True] if self.cascade else [False]):
-            g = self._get_graph(bp, greedy, cascade, penalized=penalized)
+            g = self._get_graph(bp, greedy, cascade, penalized=penalized, logprobs=logprobs)
             if g.graph is None:
                 for t in (g.valid, g.positions, g.context_lens, g.tokens):
                     t.zero_()
@@ -919,14 +990,16 @@ class LLMEngine:
         try:
             greedy = params.temperature <= 0.0
             penalized = not params.neutral
+            want_lp = params.logprobs
             t0 = time.perf_counter()
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if cuda else None
             if cuda:
                 ev[0].record()
             self.queue_prefix_copies(r)
             with tracing.span("engine.prefill", seqs=B, tokens=sum(lens) - sum(cached)):
-                # penalised requests pick their first token under the penalties too: logits
-                logits = self._prefill(prompts, tables, cached, greedy=greedy and not penalized)
+                # penalised requests pick their first token under the penalties too: logits;
+                # so do requests with logprobs, whose first token is covered like every other
+                logits = self._prefill(prompts, tables, cached, greedy=greedy and not penalized and not want_lp)
             if use_pc:
                 with tracing.span("engine.register", seqs=B):
                     self.register_prefixes(prompts, tables, r.keys)
@@ -937,7 +1010,7 @@ class LLMEngine:
             fit = self.groups_fit([n + params.max_new_tokens for n in lens])
             grouped = nshared > 0 or self.group_without_prefix(B, fit)
             g = self._get_graph(_bucket(B, self.max_batch) if self.use_graphs else B, greedy, grouped, fit,
-                                penalized)
+                                penalized, want_lp)
             if grouped:
                 g.shared_len.fill_(0)
             if nshared:
@@ -968,6 +1041,11 @@ class LLMEngine:
                 g.top_p.fill_(params.top_p)
                 if params.seed:
                     torch.manual_seed(params.seed)
+            if want_lp:
+                # every row of the batch asks for the same; the bucket's padding slots for nothing
+                ln = torch.full((g.bp,), -1, dtype=torch.int32)
+                ln[:B] = params.top_logprobs
+                _upload(g.lp_n, ln)
             if penalized:
                 # the ring starts as each prompt's tail (stream entry j at hist[b, j % W])
                 W = ops.PENALTY_WINDOW
@@ -981,14 +1059,28 @@ class LLMEngine:
                 g.rep_pen.fill_(params.repeat_penalty)
                 g.pres_pen.fill_(params.presence_penalty)
                 g.freq_pen.fill_(params.frequency_penalty)
-                first = self._penalized_greedy(logits, g) if greedy else self._select(logits, g)
+                if want_lp:
+                    first = self._pick_logprobs(logits, g)
+                else:
+                    first = self._penalized_greedy(logits, g) if greedy else self._select(logits, g)
                 rows = torch.arange(B, device=dev)
                 g.hist[rows, (g.hist_n[:B] % W).long()] = first.int()
                 g.hist_n[:B] += 1
+            elif want_lp:
+                first = self._pick_logprobs(logits, g)
             else:
                 first = logits if greedy else self._select(logits, g)
             gen = torch.empty(B, params.max_new_tokens, dtype=torch.long, device=dev)
             gen[:, 0] = first
+            glp = None
+            if want_lp:
+                # every step's logprob buffers beside ``gen`` (the first token's are the prefill's)
+                T = ops.TOP_LOGPROBS_MAX
+                glp = (torch.empty(B, params.max_new_tokens, dtype=torch.float32, device=dev),
+                       torch.empty(B, params.max_new_tokens, T, dtype=torch.int32, device=dev),
+                       torch.empty(B, params.max_new_tokens, T, dtype=torch.float32, device=dev))
+                for dst, src in zip(glp, (g.lp, g.lp_top_ids, g.lp_top)):
+                    dst[:, 0] = src[:B]
             tok = torch.zeros(g.bp, dtype=torch.int32, device=dev)
             tok[:B] = first.int()
             g.tokens.copy_(tok)
@@ -1009,10 +1101,18 @@ class LLMEngine:
                 else:
                     self._step_body(g)
                 gen[:, step] = g.out[:B]
+                if glp is not None:
+                    for dst, src in zip(glp, (g.lp, g.lp_top_ids, g.lp_top)):
+                        dst[:, step] = src[:B]
             sp_dec.__exit__(None, None, None)
             if cuda:
                 host = torch.empty(gen.shape, dtype=gen.dtype, pin_memory=True)
                 host.copy_(gen, non_blocking=True)
+                if glp is not None:
+                    hlp = tuple(torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in glp)
+                    for dst, src in zip(hlp, glp):
+                        dst.copy_(src, non_blocking=True)
+                    glp = hlp
             else:
                 host = gen
             ar_err = comm.collective_error_snapshot()
@@ -1023,7 +1123,7 @@ class LLMEngine:
             raise
         self.stats.prompt_tokens += sum(lens)
         self.stats.generated_tokens += B * params.max_new_tokens
-        return Launched(r, host, ev, params, t0, t1, ar_err)
+        return Launched(r, host, ev, params, t0, t1, ar_err, *(glp or ()))
 
     def _dump_decode(self, g: _DecodeGraph, tables, lens, nshared: int, params: SamplingParams) -> None:
         """Diagnostics: the decode attention inputs of one cascade batch, for replaying the
@@ -1045,6 +1145,35 @@ class LLMEngine:
         """Wait for a :meth:`launch`ed batch, free its KV blocks and return its tokens."""
         with tracing.span("engine.collect", seqs=h.reservation.n):
             return self._collect(h)
+
+    def collect_logprobs(self, h: "Launched") -> list[list[tuple]] | None:
+        """Per row of a :meth:`launch`ed batch with ``params.logprobs`` (else None) one
+        ``(logprob, [(id, logprob), ...])`` per generated token, the first included, cut at EOS
+        like the tokens of :meth:`collect`; the inner list holds the ``top_logprobs`` most
+        likely tokens in descending order.  Waits for the batch, frees nothing: call it before
+        or after :meth:`collect`."""
+        if h.lp is None:
+            return None
+        if h.events is not None:
+            h.events[2].synchronize()
+        comm.raise_on_collective_error(h.ar_err)
+        toks, lp, ids, top = h.host.tolist(), h.lp.tolist(), h.lp_top_ids.tolist(), h.lp_top.tolist()
+        eos = self.cfg.eos_token_id if h.params.stop_on_eos else None
+        out = []
+        for b, row in enumerate(toks):
+            n = row.index(eos) + 1 if eos in row else len(row)
+            out.append([logprob_entry(lp[b][t], ids[b][t], top[b][t]) for t in range(n)])
+        return out
+
+    @torch.inference_mode()
+    def generate_with_logprobs(self, prompts: list[list[int]], params: SamplingParams):
+        """:meth:`generate` for ``params.logprobs``: (tokens, logprobs as :meth:`collect_logprobs`)."""
+        toks, lps = [], []
+        for i in range(0, len(prompts), self.max_batch):
+            h = self.launch(prompts[i:i + self.max_batch], params)
+            lps.extend(self.collect_logprobs(h) or [])
+            toks.extend(self.collect(h))
+        return toks, lps
 
     def _collect(self, h: "Launched") -> list[list[int]]:
         try:

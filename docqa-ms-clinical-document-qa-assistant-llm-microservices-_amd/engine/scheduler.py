@@ -61,7 +61,8 @@ from .. import ops
 from ..parallel import comm
 from ..parallel.custom_ar import CollectiveError
 from ..utils import tracing
-from .llm_engine import LLMEngine, SamplingParams, _bucket, _DecodeGraph, _prefill_inputs, ring_of
+from .llm_engine import (LLMEngine, SamplingParams, _bucket, _DecodeGraph, _prefill_inputs, logprob_entry,
+                         ring_of)
 
 
 @dataclass
@@ -73,6 +74,8 @@ class Request:
     on_token: object = None          # callable(rid, token) for streaming
     stop_check: object = None        # callable(list[int]) -> bool on the output so far (stop strings)
     out: list[int] = field(default_factory=list)
+    # params.logprobs: one (logprob, [(id, logprob), ...]) per token of ``out``, parallel to it
+    logprobs: list = field(default_factory=list)
     blocks: list[int] = field(default_factory=list)
     cached: int = 0
     res: object = None   # the engine Reservation (prefix-copy pins, block keys)
@@ -139,6 +142,7 @@ class ContinuousEngine:
         self._pending = None               # (event, pinned host tokens, slot -> request) of the last step
         self._processing = None            # the readback being processed (see _process)
         self._host = None
+        self._lphost = None  # pinned (lp, top ids, top lp) buffers beside ``_host``, when first asked
         self._flip = 0
         self._mhost = None   # mixed steps' pinned token buffers (decode rows + first tokens)
         self._mflip = 0
@@ -169,7 +173,14 @@ class ContinuousEngine:
     # ------------------------------------------------------------------ client side
     def submit(self, prompt: list[int], params: SamplingParams | None = None, on_token=None,
                stop_check=None) -> cf.Future:
-        """``stop_check(out)``: called with the request's generated ids after each emitted
+        """``on_token(rid, token)`` is called for every emitted token -- and as
+        ``on_token(rid, token, (logprob, [(id, logprob), ...]))`` when ``params.logprobs`` is set:
+        a callback given with such a request must take the third argument (one that raises is
+        dropped, like every failing client callback).  The returned future resolves to the token
+        ids; its ``request`` attribute is the :class:`Request`, whose ``logprobs`` list (one
+        entry per token of the result, empty without ``params.logprobs``) is complete when the
+        future is done.
+        ``stop_check(out)``: called with the request's generated ids after each emitted
         token; a true result finishes the request there (stop strings -- the caller owns the
         tokenizer).  A check that raises is dropped, like ``on_token``."""
         params = params or SamplingParams()
@@ -185,6 +196,7 @@ class ContinuousEngine:
             stop_check = None
         r = Request(next(self._ids), list(prompt), params, fut, on_token, stop_check,
                     t_arrival=time.perf_counter())
+        fut.request = r      # the caller reads r.logprobs (parallel to the result) off the future
         with self._cv:
             # a lockstep leader queues arrivals for the next step's broadcast, so the
             # followers see exactly the waiting queue its admission sees
@@ -203,9 +215,11 @@ class ContinuousEngine:
         return [f.result() for f in futs]
 
     @torch.inference_mode()
-    def warmup(self, buckets: list[int] | None = None, sampled: bool = False, penalized: bool = False) -> None:
+    def warmup(self, buckets: list[int] | None = None, sampled: bool = False, penalized: bool = False,
+               logprobs: bool = False) -> None:
         """Capture the decode graphs of every bucket (plain and cascade; greedy, and
-        sampled if asked; their penalised flavours too if asked) before serving, so no request pays a capture / GEMM-tuning
+        sampled if asked; their penalised flavours too if asked; ``logprobs``: the logprob flavour
+        of each as well) before serving, so no request pays a capture / GEMM-tuning
         stall mid-stream.  Slots are empty (valid 0): the captured warm-up steps write
         nothing to the KV cache."""
         if not self.eng.use_graphs or self.running:
@@ -220,11 +234,12 @@ class ContinuousEngine:
             for greedy in ([True, False] if sampled else [True]):
                 for c in casc:
                     for pen in ([False, True] if penalized else [False]):
-                        g = self._graph(bp, greedy, c, penalized=pen)
-                        if g.graph is None:
-                            if self._pool is None:
-                                self._pool = torch.cuda.graph_pool_handle()
-                            self.eng._capture(g, self._pool)
+                        for lp in ([False, True] if logprobs else [False]):
+                            g = self._graph(bp, greedy, c, penalized=pen, logprobs=lp)
+                            if g.graph is None:
+                                if self._pool is None:
+                                    self._pool = torch.cuda.graph_pool_handle()
+                                self.eng._capture(g, self._pool)
 
     # ------------------------------------------------------------------ serving thread
     def start(self) -> "ContinuousEngine":
@@ -453,8 +468,9 @@ class ContinuousEngine:
                 out = eng._prefill([r.prompt for r in adm], [r.blocks for r in adm], [r.cached for r in adm],
                                    greedy=greedy)
                 err = comm.collective_error_snapshot()
+                first_lp: list = [None] * len(adm)
                 first = out.tolist() if greedy else self._sample_rows(out, [r.params for r in adm],
-                                                                          [self._stream(r) for r in adm])
+                                                                          [self._stream(r) for r in adm], first_lp)
                 comm.raise_on_collective_error(err)
         except CollectiveError:
             for r in adm:
@@ -475,9 +491,9 @@ class ContinuousEngine:
         eng.stats.prompt_tokens += sum(len(r.prompt) for r in adm)
         eng.stats.cached_tokens += sum(r.cached for r in adm)
         joined = []
-        for r, t in zip(adm, first):
+        for r, t, lp in zip(adm, first, first_lp):
             r.t_first = now
-            self._emit(r, t)
+            self._emit(r, t, lp)
             if self._finished(r):
                 r.done = True
                 self._retire(r)
@@ -674,6 +690,7 @@ class ContinuousEngine:
         hn = torch.zeros(k, dtype=torch.int32)
         ln = torch.zeros(k, dtype=torch.int32)
         pen = torch.tensor([[1.0, 0.0, 0.0]] * k, dtype=torch.float32)
+        lpn = torch.tensor([r.params.lp_n for r in reqs], dtype=torch.int32)   # -1: did not ask
         for i, r in enumerate(reqs):
             if not r.params.neutral:
                 hist[i], hn[i] = ring_of(self._stream(r), W)
@@ -706,6 +723,7 @@ class ContinuousEngine:
         m.rep_pen[sl].copy_(pen[:, 0].contiguous().to(dev, non_blocking=True))
         m.pres_pen[sl].copy_(pen[:, 1].contiguous().to(dev, non_blocking=True))
         m.freq_pen[sl].copy_(pen[:, 2].contiguous().to(dev, non_blocking=True))
+        m.lp_n[sl].copy_(lpn.to(dev, non_blocking=True))
         self.running.extend(reqs)
         self._version += 1
 
@@ -716,11 +734,31 @@ class ContinuousEngine:
         return r.prompt[:r.orig_len if r.orig_len >= 0 else len(r.prompt)] + r.out
 
     def _sample_rows(self, logits: torch.Tensor, params: list[SamplingParams],
-                     streams: list[list[int]] | None = None) -> list[int]:
+                     streams: list[list[int]] | None = None, lp_out: list | None = None) -> list[int]:
         """First tokens of admitted requests from their prefill logits; ``streams``: each
-        request's tokens so far, the penalty window of the penalised ones."""
+        request's tokens so far, the penalty window of the penalised ones.  ``lp_out``: a list
+        with one slot per request that receives the first token's (logprob, top list) of the
+        requests that ask for logprobs, from these logits as the LM head wrote them."""
+        if lp_out is None or not any(p.logprobs for p in params):
+            return self._pick_rows(logits, params, streams)
+        # the penalised greedy pick clobbers its input: it gets a copy, the logprobs the original
+        ids = self._pick_rows(logits, params, streams, keep=True)
+        full = self.eng.model.full_logits(logits)
+        dev = full.device
+        lp, ti, tl = ops.token_logprobs(full, self.eng.cfg.vocab_size, torch.tensor(ids, dtype=torch.long, device=dev),
+                                        torch.tensor([p.lp_n for p in params], dtype=torch.int32, device=dev))
+        lp, ti, tl = lp.tolist(), ti.tolist(), tl.tolist()
+        for i, p in enumerate(params):
+            if p.logprobs:
+                lp_out[i] = logprob_entry(lp[i], ti[i], tl[i])
+        return ids
+
+    def _pick_rows(self, logits: torch.Tensor, params: list[SamplingParams],
+                   streams: list[list[int]] | None = None, keep: bool = False) -> list[int]:
+        """The pick of :meth:`_sample_rows`; ``keep``: ``logits`` must survive it unchanged."""
         model = self.eng.model
-        if all(p.fused_greedy_ok for p in params):
+        if all(p.temperature <= 0.0 and p.neutral for p in params):
+            # greedy neutral rows (with logprobs: the argmax of the logits they come from)
             return model.greedy(logits).tolist()
         full = model.full_logits(logits)
         dev = full.device
@@ -735,7 +773,7 @@ class ContinuousEngine:
                    torch.tensor([p.presence_penalty for p in params], dtype=torch.float32, device=dev),
                    torch.tensor([p.frequency_penalty for p in params], dtype=torch.float32, device=dev))
             if all(p.temperature <= 0 for p in params):
-                return ops.penalized_argmax(full, full.shape[1], *pen).tolist()
+                return ops.penalized_argmax(full.clone() if keep else full, full.shape[1], *pen).tolist()
         if pen is not None and (full.dtype == torch.float32):
             full = full.clone(memory_format=torch.contiguous_format)
         full = full.float()
@@ -748,14 +786,15 @@ class ContinuousEngine:
         return ops.sample(full, it, tk, tp, u).tolist()
 
     def _graph(self, bp: int, greedy: bool, cascade: bool, fit: bool = True,
-               penalized: bool = False) -> _DecodeGraph:
+               penalized: bool = False, logprobs: bool = False) -> _DecodeGraph:
         fit = fit or self._master.groups_fit
-        key = (bp, greedy, cascade, fit, penalized)
+        key = (bp, greedy, cascade, fit, penalized, logprobs)
         g = self._graphs.get(key)
         if g is None:
             g = _DecodeGraph.view_of(self._master, bp)
             g.greedy, g.cascade, g.groups_fit = greedy, cascade, fit
             g.penalized = penalized
+            g.logprobs = logprobs
             self._graphs[key] = g
         return g
 
@@ -848,7 +887,9 @@ class ContinuousEngine:
         penalized = not all(r.params.neutral for r in self.running)
         fit = self._groups_fit()
         grouped = self._nshared > 0 or eng.group_without_prefix(n, fit)
-        g = self._graph(bp, greedy, grouped, fit, penalized)
+        # any running row asks for logprobs: the flavour that computes them (for those rows only)
+        want_lp = any(r.params.logprobs for r in self.running)
+        g = self._graph(bp, greedy, grouped, fit, penalized, want_lp)
         if eng.lpt:
             # re-rank only when the running set changed (admission / retirement)
             eng.set_order(g, [len(r.prompt) + len(r.out) for r in self.running], key=self._version)
@@ -876,18 +917,32 @@ class ContinuousEngine:
                 if self._host is None:
                     self._host = [torch.empty(eng.max_batch, dtype=torch.long, pin_memory=True) for _ in range(2)]
                 host = self._host[self._flip]
-                self._flip ^= 1
                 host[:n].copy_(g.out[:n], non_blocking=True)
+                lph = None
+                if want_lp:
+                    # the step's logprob buffers ride to the host next to its tokens
+                    if self._lphost is None:
+                        T = ops.TOP_LOGPROBS_MAX
+                        self._lphost = [(torch.empty(eng.max_batch, dtype=torch.float32, pin_memory=True),
+                                         torch.empty(eng.max_batch, T, dtype=torch.int32, pin_memory=True),
+                                         torch.empty(eng.max_batch, T, dtype=torch.float32, pin_memory=True))
+                                        for _ in range(2)]
+                    lph = self._lphost[self._flip]
+                    for dst, src in zip(lph, (g.lp, g.lp_top_ids, g.lp_top)):
+                        dst[:n].copy_(src[:n], non_blocking=True)
+                self._flip ^= 1
                 err = comm.collective_error_snapshot()
                 ev = torch.cuda.Event()
                 ev.record()
             else:
                 host, err, ev = g.out[:n].clone(), comm.collective_error_snapshot(), None
-            prev, self._pending = self._pending, (ev, host, snap, err)
+                lph = tuple(t[:n].clone() for t in (g.lp, g.lp_top_ids, g.lp_top)) if want_lp else None
+            prev, self._pending = self._pending, (ev, host, snap, err, lph)
             if prev is not None:
                 self._process(prev)          # step t-1's tokens while step t runs
         else:
-            self._process((None, g.out[:n].clone(), snap, comm.collective_error_snapshot()))
+            lph = tuple(t[:n].clone() for t in (g.lp, g.lp_top_ids, g.lp_top)) if want_lp else None
+            self._process((None, g.out[:n].clone(), snap, comm.collective_error_snapshot(), lph))
         eng.stats.decode_s += time.perf_counter() - t0
 
     def _process(self, pending) -> None:
@@ -903,16 +958,17 @@ class ContinuousEngine:
         if isinstance(pending[0], str):      # ("mixed", ...): a mixed step's readback
             self._process_mixed(pending)
             return
-        ev, host, snap, err = pending
+        ev, host, snap, err, lph = pending
         if ev is not None:
             ev.synchronize()
         comm.raise_on_collective_error(err)
         toks = host[:len(snap)].tolist()
+        lp, ti, tl = [t[:len(snap)].tolist() for t in lph] if lph is not None else (None, None, None)
         finished = []
-        for r, t in zip(snap, toks):
+        for i, (r, t) in enumerate(zip(snap, toks)):
             if r.done:
                 continue                      # the extra lagged step of a finished request
-            self._emit(r, t)
+            self._emit(r, t, logprob_entry(lp[i], ti[i], tl[i]) if lp is not None and r.params.logprobs else None)
             if self._finished(r):
                 r.done = True
                 finished.append(r)
@@ -923,12 +979,19 @@ class ContinuousEngine:
             self._compact(keep)
             self._update_shared()
 
-    def _emit(self, r: Request, tok: int) -> None:
+    def _emit(self, r: Request, tok: int, lp: tuple | None = None) -> None:
+        """``lp``: the token's (logprob, top list), for a request that asked; its ``on_token``
+        is then called with it as a third argument."""
         r.out.append(int(tok))
+        if r.params.logprobs:
+            r.logprobs.append(lp)
         self.generated += 1
         if r.on_token is not None:
             try:
-                r.on_token(r.rid, int(tok))
+                if r.params.logprobs:
+                    r.on_token(r.rid, int(tok), lp)
+                else:
+                    r.on_token(r.rid, int(tok))
             except Exception:  # noqa: BLE001 - a client callback must not stop the engine
                 r.on_token = None
 
@@ -958,9 +1021,10 @@ class ContinuousEngine:
         if keep != list(range(k)):
             idx = torch.tensor(keep, dtype=torch.long, device=m.tokens.device)
             for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
-                         "top_k", "top_p", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen"):
+                         "top_k", "top_p", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen", "lp_n"):
                 t = getattr(m, name)
                 t[:k] = t[idx]
+        m.lp_n[k:n].fill_(-1)
         m.valid[k:n].zero_()
         m.context_lens[k:n].zero_()
         m.positions[k:n].zero_()

@@ -1416,6 +1416,34 @@ def penalized_argmax(logits, n_valid: int, hist, hist_n, last_n, rep_pen, pres_p
     return ref.penalized_argmax(logits, n_valid, hist, hist_n, last_n, rep_pen, pres_pen, freq_pen, valid)
 
 
+TOP_LOGPROBS_MAX = ref.TOP_LOGPROBS_MAX   # columns of the top list of :func:`token_logprobs`
+
+
+def token_logprobs(logits, n_valid: int, chosen, top_n, lp=None, top_ids=None, top_lp=None):
+    """Per-token log-probabilities of the LM-head logits [R, ld] (bf16 or fp32, read as they are):
+    ``logprob(t) = logit[t] - logsumexp(logit[0:n_valid])``; columns at or past ``n_valid`` take
+    no part.  ``chosen`` [R] int64 is the picked token of each row, ``top_n`` [R] int32 what the
+    row wants: -1 nothing (none of its outputs is written), 0 the chosen token's logprob, 1..20
+    also that many most likely tokens.  Returns ``(lp [R] fp32, top_ids [R, 20] int32, top_lp
+    [R, 20] fp32)``, written into the caller's buffers where given (a decode graph's static slot
+    buffers; fresh ones are filled with the -1 row's sentinels 0 / -1 / -inf).  The top list is
+    in descending order, ties to the lower id; entries past ``top_n`` or past the vocabulary are
+    (-1, -inf).  On a GPU (csrc/kernels/logprobs.hip) the row stride must be a multiple of 16
+    bytes and bf16 logits need ``n_valid % 8 == 0``; logits are expected finite."""
+    R, dev = logits.shape[0], logits.device
+    if lp is None:
+        lp = torch.zeros(R, dtype=torch.float32, device=dev)
+    if top_ids is None:
+        top_ids = torch.full((R, TOP_LOGPROBS_MAX), -1, dtype=torch.int32, device=dev)
+    if top_lp is None:
+        top_lp = torch.full((R, TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=dev)
+    if _gpu(logits):
+        _native().token_logprobs(logits, int(n_valid), chosen, top_n, lp, top_ids, top_lp)
+    else:
+        ref.token_logprobs(logits, int(n_valid), chosen, top_n, lp, top_ids, top_lp)
+    return lp, top_ids, top_lp
+
+
 def decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n) -> None:
     """:func:`decode_advance`, and the valid rows' new token joins their ring:
     hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1."""

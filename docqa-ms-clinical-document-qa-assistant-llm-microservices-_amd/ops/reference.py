@@ -510,6 +510,33 @@ def penalized_argmax(logits, n_valid: int, hist, hist_n, last_n, rep_pen, pres_p
     return x.argmax(dim=-1)
 
 
+TOP_LOGPROBS_MAX = 20   # columns of the top list (logprobs.hip kTop)
+
+
+def token_logprobs(logits, n_valid: int, chosen, top_n, lp, top_ids, top_lp) -> None:
+    """Per-token log-probabilities in fp32, in place on lp [R], top_ids / top_lp [R, 20]:
+    lp[r] = logit[r, chosen[r]] - logsumexp(logit[r, :n_valid]) and the top_n[r] most likely
+    tokens in descending order, ties to the lower id; entries past top_n[r] (or past n_valid)
+    are (-1, -inf).  Rows with top_n[r] < 0 are left untouched.  Values are formed as
+    (x - max) - log(sum exp(x - max)), like the kernel."""
+    x = logits[:, :n_valid].float()
+    for r in range(x.shape[0]):
+        tn = min(int(top_n[r]), TOP_LOGPROBS_MAX)
+        if tn < 0:
+            continue
+        d = x[r] - x[r].max()
+        rel = d - torch.log(torch.exp(d).sum())
+        c = int(chosen[r])
+        lp[r] = rel[c] if 0 <= c < n_valid else -math.inf
+        top_ids[r] = -1
+        top_lp[r] = -math.inf
+        k = min(tn, n_valid)
+        if k > 0:
+            ids = torch.sort(x[r], descending=True, stable=True).indices[:k]   # stable: the lower id first
+            top_ids[r, :k] = ids.to(top_ids.dtype)
+            top_lp[r, :k] = rel[ids]
+
+
 def decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n) -> None:
     W = hist.shape[1]
     rows = torch.nonzero(valid.bool())[:, 0]

@@ -11,7 +11,8 @@ other request in flight) instead of a llama.cpp process.
   POST /api/chat      {"model", "messages": [{"role", "content"}], "stream" (default true),
                        "options": {"temperature", "num_predict", "top_k", "top_p", "seed",
                                    "repeat_penalty", "repeat_last_n", "presence_penalty",
-                                   "frequency_penalty", "stop"}}
+                                   "frequency_penalty", "stop"},
+                       "logprobs" (default false), "top_logprobs" (0..20)}
                       -> {"model", "created_at", "message": {"role": "assistant", "content"},
                           "done": true, "done_reason": "stop" | "length", "total_duration",
                           "load_duration", "prompt_eval_count", "prompt_eval_duration",
@@ -19,6 +20,17 @@ other request in flight) instead of a llama.cpp process.
                       stream: application/x-ndjson, one line per text piece
                       ({"message": {..., "content": piece}, "done": false}) then the final
                       line above with an empty content
+                      logprobs: the response gains "logprobs", one {"token", "logprob", "bytes",
+                      "top_logprobs": [{"token", "logprob", "bytes"} x top_logprobs]} per generated
+                      token -- the log-probability of the model's own distribution (the LM head's
+                      logits before penalties, temperature, top-k and top-p; engine/llm_engine.py).
+                      Streamed, each line carries the entries of the tokens whose text it releases
+                      (a token held back for an incomplete UTF-8 sequence or a possible stop string
+                      travels with the line that releases it, or with the final line); over all
+                      lines they are the non-streamed list.  Tokens a stop string cuts off are
+                      dropped from it like their text: a token wholly behind the cut goes, a token
+                      whose text straddles it (part of it is in the response) keeps its entry.  "top_logprobs" outside 0..20, or above 0
+                      without "logprobs", is a 400 {"error"}.
   POST /api/generate  {"model", "prompt", "system", "raw", "stream", "options"} -> the same
                       with "response" instead of "message"
   GET  /api/tags      the one model this process serves; GET /api/version
@@ -60,6 +72,8 @@ class OllamaChatRequest(BaseModel):
     messages: list[OllamaMessage] = []
     stream: bool = True
     options: dict | None = None
+    logprobs: bool = False
+    top_logprobs: int = 0
 
 
 class OllamaGenerateRequest(BaseModel):
@@ -69,6 +83,8 @@ class OllamaGenerateRequest(BaseModel):
     raw: bool = False
     stream: bool = True
     options: dict | None = None
+    logprobs: bool = False
+    top_logprobs: int = 0
 
 
 def _now() -> str:
@@ -122,6 +138,43 @@ def held_back(text: str, stops: list[str]) -> int:
     return best
 
 
+TOP_LOGPROBS_MAX = 20   # Ollama's limit, and ops.TOP_LOGPROBS_MAX
+
+
+def logprobs_error(logprobs: bool, top_logprobs: int) -> str | None:
+    """Why the request's logprob fields are refused (HTTP 400), or None."""
+    if not 0 <= top_logprobs <= TOP_LOGPROBS_MAX:
+        return f"top_logprobs must be between 0 and {TOP_LOGPROBS_MAX}"
+    if top_logprobs > 0 and not logprobs:
+        return "top_logprobs requires logprobs to be true"
+    return None
+
+
+def logprob_entries(tok, ids: list[int], lps: list) -> list[dict]:
+    """Ollama's per-token objects from token ids and the engine's (logprob, [(id, logprob), ...])
+    of each: ``token`` is the tokenizer's decoding of that single id, ``bytes`` its UTF-8 bytes."""
+    def one(i: int, lp: float) -> dict:
+        t = tok.decode([i])
+        return {"token": t, "logprob": max(float(lp), -3.4028234663852886e38), "bytes": list(t.encode("utf-8"))}
+
+    return [{**one(i, lp), "top_logprobs": [one(j, v) for j, v in top]} for i, (lp, top) in zip(ids, lps)]
+
+
+def visible_tokens(tok, ids: list[int], start: int, length: int) -> int:
+    """The smallest n >= ``start`` whose tokens ids[:n] decode to at least ``length`` characters
+    (a trailing incomplete UTF-8 sequence not counted): the tokens a text of that length shows,
+    wholly or in part -- a token that straddles a stop string's cut keeps its entry, since part of
+    its text is in the response.  len(ids) when even all of them do not.  Trailing U+FFFD are taken
+    for an incomplete sequence, as the streaming loop takes them: a model that really emits U+FFFD
+    as the last character of a prefix has that token counted one piece late (with the next
+    character or the final line), never dropped.  Each call decodes a few growing prefixes, which
+    is fine at num_predict sizes."""
+    n = start
+    while n < len(ids) and len(tok.decode(ids[:n]).rstrip("\ufffd")) < length:
+        n += 1
+    return n
+
+
 def register(app: FastAPI, settings, metrics) -> None:
     """Add the Ollama routes to the llm-qa app (``app.state.pipeline`` / ``app.state.batcher``)."""
 
@@ -129,23 +182,28 @@ def register(app: FastAPI, settings, metrics) -> None:
         lim = pipe.max_prompt_tokens
         return ids if not lim or len(ids) <= lim else ids[: lim // 2] + ids[-(lim // 2):]
 
-    async def _run(kind: str, model: str, ids: list[int], options: dict | None, stream: bool):
+    async def _run(kind: str, model: str, ids: list[int], options: dict | None, stream: bool,
+                   logprobs: bool = False, top_logprobs: int = 0):
         pipe, batcher = app.state.pipeline, app.state.batcher
         if pipe is None or batcher is None:
             return JSONResponse(status_code=503, content={"error": "model not loaded"})
+        bad = logprobs_error(logprobs, top_logprobs)
+        if bad:
+            return JSONResponse(status_code=400, content={"error": bad})
         tok = pipe.chat_tok
         ids = _prompt_ids(pipe, ids)
         params = sampling_from_options(options, settings, pipe.engine.max_context, len(ids))
+        params.logprobs, params.top_logprobs = bool(logprobs), int(top_logprobs)
         metrics.inc(f"ollama_{kind}_requests")
         loop = asyncio.get_running_loop()
         q: asyncio.Queue = asyncio.Queue()
         t0 = time.perf_counter()
         first = [0.0]
 
-        def on_token(_rid, t):
+        def on_token(_rid, t, lp=None):     # the scheduler adds the token's logprobs when asked
             if not first[0]:
                 first[0] = time.perf_counter()
-            loop.call_soon_threadsafe(q.put_nowait, t)
+            loop.call_soon_threadsafe(q.put_nowait, (t, lp))
 
         stops = stop_strings(options)
         # the scheduler retires the request at the token that completes a stop string (the
@@ -176,19 +234,30 @@ def register(app: FastAPI, settings, metrics) -> None:
                 d["context"] = []
             return d
 
+        def entries(out: list[int], lps: list, lo: int, hi: int) -> list[dict]:
+            return logprob_entries(tok, out[lo:hi], lps[lo:hi])
+
         if not stream:
             res = await asyncio.wrap_future(fut)
             text, stopped = cut(tok.decode(res["ids"]))
-            return JSONResponse(final(res["ids"], text, stopped))
+            d = final(res["ids"], text, stopped)
+            if logprobs:
+                # a stop string's cut drops the tokens whose text it drops
+                n = visible_tokens(tok, res["ids"], 0, len(text)) if stopped else len(res["ids"])
+                d["logprobs"] = entries(res["ids"], res["logprobs"], 0, n)
+            return JSONResponse(d)
 
         async def lines():
             got: list[int] = []
+            glp: list = []   # logprobs: each token's (logprob, top list), parallel to ``got``
             sent = ""
+            shown = 0        # tokens whose logprob entries have gone out
             while True:
                 item = await q.get()
                 if item is _DONE:
                     break
-                got.append(item)
+                got.append(item[0])
+                glp.append(item[1])
                 text = tok.decode(got)
                 if text.endswith("\ufffd"):     # an incomplete UTF-8 sequence: wait for its bytes
                     continue
@@ -200,19 +269,31 @@ def register(app: FastAPI, settings, metrics) -> None:
                         continue
                 piece, sent = text[len(sent):], text
                 if piece:
-                    yield json.dumps({"model": model or settings.llm_model, "created_at": _now(), **body(piece),
-                                      "done": False}) + "\n"
+                    d = {"model": model or settings.llm_model, "created_at": _now(), **body(piece), "done": False}
+                    if logprobs:
+                        # the entries of the tokens this piece makes visible
+                        n = visible_tokens(tok, got, shown, len(sent))
+                        d["logprobs"], shown = entries(got, glp, shown, n), n
+                    yield json.dumps(d) + "\n"
             try:
-                out = fut.result()["ids"]
+                res = fut.result()
+                out = res["ids"]
             except Exception as e:  # noqa: BLE001 - the stream is already open: report in-band
                 yield json.dumps({"error": f"{type(e).__name__}: {e}"}) + "\n"
                 return
             text, stopped = cut(tok.decode(out))
             rest = text[len(sent):] if text.startswith(sent) else text
             if rest:     # the static batcher (no per-token callback) or a held-back tail
-                yield json.dumps({"model": model or settings.llm_model, "created_at": _now(), **body(rest),
-                                  "done": False}) + "\n"
-            yield json.dumps(final(out, "", stopped)) + "\n"
+                d = {"model": model or settings.llm_model, "created_at": _now(), **body(rest), "done": False}
+                if logprobs:
+                    n = visible_tokens(tok, out, shown, len(text))
+                    d["logprobs"], shown = entries(out, res["logprobs"], shown, n), n
+                yield json.dumps(d) + "\n"
+            d = final(out, "", stopped)
+            if logprobs:
+                n = visible_tokens(tok, out, shown, len(text)) if stopped else len(out)
+                d["logprobs"] = entries(out, res["logprobs"], shown, n)
+            yield json.dumps(d) + "\n"
 
         return StreamingResponse(lines(), media_type="application/x-ndjson")
 
@@ -222,7 +303,7 @@ def register(app: FastAPI, settings, metrics) -> None:
         if pipe is None:
             return JSONResponse(status_code=503, content={"error": "model not loaded"})
         ids = pipe.chat_tok.chat_messages([m.model_dump() for m in req.messages])
-        return await _run("chat", req.model, ids, req.options, req.stream)
+        return await _run("chat", req.model, ids, req.options, req.stream, req.logprobs, req.top_logprobs)
 
     @app.post("/api/generate")
     async def ollama_generate(req: OllamaGenerateRequest):
@@ -234,7 +315,7 @@ def register(app: FastAPI, settings, metrics) -> None:
             ids = tok.encode(req.prompt)
         else:
             ids = tok.chat_prompt(req.prompt, system=req.system)
-        return await _run("generate", req.model, ids, req.options, req.stream)
+        return await _run("generate", req.model, ids, req.options, req.stream, req.logprobs, req.top_logprobs)
 
     @app.get("/api/tags")
     def ollama_tags():

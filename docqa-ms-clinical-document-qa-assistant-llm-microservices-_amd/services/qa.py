@@ -103,13 +103,17 @@ class DynamicBatcher:
             for b in gens:
                 p = b[1]["params"]
                 groups.setdefault((p.max_new_tokens, p.temperature, p.top_k, p.top_p, p.stop_on_eos, p.seed,
-                                   p.repeat_penalty, p.repeat_last_n, p.presence_penalty, p.frequency_penalty),
-                                  []).append(b)
+                                   p.repeat_penalty, p.repeat_last_n, p.presence_penalty, p.frequency_penalty,
+                                   p.logprobs, p.top_logprobs), []).append(b)
             for grp in groups.values():
-                outs = self.pipe.engine.generate([b[1]["ids"] for b in grp], grp[0][1]["params"])
-                for (_, _, f, t0), o in zip(grp, outs):
+                p = grp[0][1]["params"]
+                if p.logprobs:
+                    outs, lps = self.pipe.engine.generate_with_logprobs([b[1]["ids"] for b in grp], p)
+                else:
+                    outs, lps = self.pipe.engine.generate([b[1]["ids"] for b in grp], p), None
+                for i, ((_, _, f, t0), o) in enumerate(zip(grp, outs)):
                     self.metrics.observe("generate_latency_s", time.perf_counter() - t0)
-                    f.set_result({"ids": list(o)})
+                    f.set_result({"ids": list(o), **({"logprobs": lps[i]} if lps is not None else {})})
             if sums:
                 prompts = [self.pipe.chat_tok.chat_prompt(b[1]) for b in sums]
                 lim = self.pipe.max_prompt_tokens
@@ -297,7 +301,9 @@ class ContinuousBatcher:
                     f.set_exception(ef.exception())
                     return
                 self.metrics.observe("generate_latency_s", time.perf_counter() - t0)
-                f.set_result({"ids": list(ef.result())})
+                req = getattr(ef, "request", None)
+                lps = {"logprobs": list(req.logprobs)} if req is not None and req.params.logprobs else {}
+                f.set_result({"ids": list(ef.result()), **lps})
 
             self.engine.submit(g["ids"], g["params"], g.get("on_token"),
                                g.get("stop_check")).add_done_callback(gdone)
