@@ -495,6 +495,67 @@ at::Tensor penalized_argmax(at::Tensor logits, int64_t n_valid, const at::Tensor
   return out;
 }
 
+// ---- seeded sampling (sample.hip) ----------------------------------------------------------
+// seed [R] int64, index [R] int32 -> fp32 [R]: Philox4x32-10 of key seed, counter (index, 0, 0, 0)
+at::Tensor seeded_uniform(const at::Tensor& seed, const at::Tensor& index) {
+  CHECK_GPU(seed);
+  TORCH_CHECK(seed.scalar_type() == at::kLong && seed.is_contiguous(), "seeded_uniform: seed must be contiguous int64");
+  TORCH_CHECK(index.scalar_type() == at::kInt && index.is_contiguous() && index.device() == seed.device() &&
+                  index.numel() == seed.numel(), "seeded_uniform: index must be contiguous int32, one per seed");
+  c10::DeviceGuard g(seed.device());
+  auto out = at::empty({seed.numel()}, seed.options().dtype(at::kFloat));
+  CHECK_RC(docqa_seeded_uniform(seed.data_ptr<int64_t>(), index.data_ptr<int>(), out.data_ptr<float>(),
+                                (int)seed.numel(), stream()), "seeded_uniform");
+  return out;
+}
+
+// logits [R, ld] bf16 / fp32 with unit column stride, any row stride and alignment; per-row
+// parameters hold at least R entries (bucket-sized tensors are fine); exactly one of u and
+// (seed, index); min_p / valid may be None -> int64 [R]
+at::Tensor sample_tokens(const at::Tensor& logits, int64_t n_valid, const at::Tensor& inv_temp,
+                         const at::Tensor& top_k, const at::Tensor& top_p, const c10::optional<at::Tensor>& min_p,
+                         const c10::optional<at::Tensor>& u, const c10::optional<at::Tensor>& seed,
+                         const c10::optional<at::Tensor>& index, const c10::optional<at::Tensor>& valid) {
+  CHECK_GPU(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "sample_tokens wants [rows, V] with unit stride");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "sample_tokens: bf16 or fp32 logits");
+  const int64_t R = logits.size(0), V = logits.size(1), ld = logits.stride(0);
+  TORCH_CHECK(n_valid >= 1 && n_valid <= V, "sample_tokens: n_valid must be in [1, V]");
+  TORCH_CHECK(R <= 1 || ld >= V, "sample_tokens: row stride below V");
+  TORCH_CHECK(ld < (int64_t(1) << 31), "sample_tokens: row stride too large");
+  const auto opt = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); };
+  const auto check_row_param = [&](const at::Tensor& t, at::ScalarType ty, const char* name) {
+    TORCH_CHECK(t.scalar_type() == ty, "sample_tokens: ", name, " has the wrong dtype");
+    TORCH_CHECK(t.device() == logits.device(), "sample_tokens: ", name, " must be on the logits' device");
+    TORCH_CHECK(t.is_contiguous(), "sample_tokens: ", name, " must be contiguous");
+    TORCH_CHECK(t.numel() >= R, "sample_tokens: ", name, " has ", t.numel(), " entries for ", R, " rows");
+  };
+  check_row_param(inv_temp, at::kFloat, "inv_temp");
+  check_row_param(top_k, at::kInt, "top_k");
+  check_row_param(top_p, at::kFloat, "top_p");
+  if (opt(min_p)) check_row_param(*min_p, at::kFloat, "min_p");
+  if (opt(valid)) check_row_param(*valid, at::kInt, "valid");
+  TORCH_CHECK(opt(u) != opt(seed), "sample_tokens: exactly one of u and seed");
+  TORCH_CHECK(opt(seed) == opt(index), "sample_tokens: seed and index go together");
+  if (opt(u)) check_row_param(*u, at::kFloat, "u");
+  if (opt(seed)) {
+    check_row_param(*seed, at::kLong, "seed");
+    check_row_param(*index, at::kInt, "index");
+  }
+  c10::DeviceGuard g(logits.device());
+  auto out = at::empty({R}, logits.options().dtype(at::kLong));
+  CHECK_RC(docqa_sample_tokens(logits.data_ptr(), (int)R, (int)n_valid, (int)ld, bf ? 1 : 0,
+                               inv_temp.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                               opt(min_p) ? min_p->data_ptr<float>() : nullptr,
+                               opt(u) ? u->data_ptr<float>() : nullptr,
+                               opt(seed) ? seed->data_ptr<int64_t>() : nullptr,
+                               opt(index) ? index->data_ptr<int>() : nullptr,
+                               opt(valid) ? valid->data_ptr<int>() : nullptr, out.data_ptr<int64_t>(), stream()),
+           "sample_tokens");
+  return out;
+}
+
 // ---- per-token log-probabilities -----------------------------------------------------------
 // logits [R, >= n_valid] bf16 / fp32 (row stride a multiple of 16 bytes; bf16: n_valid % 8 == 0),
 // chosen [R] int64, top_n [R] int32 (-1: skip the row, 0: the chosen logprob only, 1..20: also
@@ -1855,6 +1916,9 @@ TORCH_LIBRARY(docqa, m) {
   m.def("decode_slots(Tensor block_tables, Tensor positions, Tensor valid, int BS) -> Tensor");
   m.def("decode_advance(Tensor nxt, Tensor(a!) out, Tensor(b!) tokens, Tensor(c!) positions, Tensor(d!) context_lens, Tensor valid) -> ()");
   m.def("sample(Tensor logits, Tensor inv_temp, Tensor top_k, Tensor top_p, Tensor u) -> Tensor");
+  m.def("seeded_uniform(Tensor seed, Tensor index) -> Tensor");
+  m.def("sample_tokens(Tensor logits, int n_valid, Tensor inv_temp, Tensor top_k, Tensor top_p, Tensor? min_p=None, "
+        "Tensor? u=None, Tensor? seed=None, Tensor? index=None, Tensor? valid=None) -> Tensor");
   m.def("penalty_window() -> int", &penalty_window);
   m.def("apply_penalties(Tensor(a!) logits, Tensor hist, Tensor hist_n, Tensor last_n, Tensor rep_pen, "
         "Tensor pres_pen, Tensor freq_pen, Tensor? valid=None) -> ()");
@@ -1976,6 +2040,8 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("decode_slots", &decode_slots);
   m.impl("decode_advance", &decode_advance);
   m.impl("sample", &sample);
+  m.impl("seeded_uniform", &seeded_uniform);
+  m.impl("sample_tokens", &sample_tokens);
   m.impl("apply_penalties", &apply_penalties);
   m.impl("penalized_argmax", &penalized_argmax);
   m.impl("token_logprobs", &token_logprobs);

@@ -66,6 +66,12 @@ int docqa_token_cls_argmax(const void* h, int ldh, const void* w, const void* bi
 int docqa_sample(const float* logits, int rows, int V, int ld, const float* inv_temp,
                  const int* top_k, const float* top_p, const float* u, int64_t* out,
                  hipStream_t s);
+// sample.hip: Philox4x32-10 uniforms of (seed, index), and the one-read sampler over bf16 /
+// fp32 logits (columns < n_valid).  Exactly one of u / (seed, index); min_p, valid may be null.
+int docqa_seeded_uniform(const int64_t* seed, const int* index, float* out, int n, hipStream_t s);
+int docqa_sample_tokens(const void* logits, int rows, int n_valid, int ld, int is_bf16, const float* inv_temp,
+                        const int* top_k, const float* top_p, const float* min_p, const float* u,
+                        const int64_t* seed, const int* index, const int* valid, int64_t* out, hipStream_t s);
 
 // repeat / presence / frequency penalties over a per-row token ring hist [rows, W] (W must be
 // docqa_penalty_window()), hist_n [rows] tokens appended so far; valid may be null (all rows)

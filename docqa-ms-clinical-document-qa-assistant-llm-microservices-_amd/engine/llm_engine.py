@@ -42,10 +42,18 @@ _DECODE_DUMP_SKIP = [int(os.environ.get("DOCQA_DECODE_DUMP_SKIP", "1"))]
 
 @dataclass
 class SamplingParams:
+    """``seed`` (0: unset) and reproducibility: the continuous scheduler (the service's default)
+    draws every token of a sampled request from ``ops.seeded_uniform(seed, position)``, so the
+    same prompt, options and seed give the same tokens whatever else is in flight, in whichever
+    slot, across preemptions and on every TP rank; an unseeded request gets a random seed of its
+    own at submission.  The static batcher (:meth:`LLMEngine.launch` / ``generate``) reproduces
+    per BATCH: it seeds torch's generator once and draws one ``torch.rand(B)`` per step."""
     max_new_tokens: int = 128
     temperature: float = 0.0      # 0 -> greedy (the reference's ChatOllama temperature=0)
     top_k: int = 0
     top_p: float = 1.0
+    # keep only tokens with p >= min_p * p_max (0: off), after temperature like top-k / top-p
+    min_p: float = 0.0
     stop_on_eos: bool = True
     seed: int = 0
     # llama.cpp's penalty sampler over the last ``repeat_last_n`` tokens of prompt + output
@@ -283,6 +291,11 @@ class _DecodeGraph:
         self.inv_temp = torch.ones(bp, dtype=torch.float32, device=dev)
         self.top_k = torch.zeros(bp, dtype=torch.int32, device=dev)
         self.top_p = torch.ones(bp, dtype=torch.float32, device=dev)
+        self.min_p = torch.zeros(bp, dtype=torch.float32, device=dev)
+        # per-slot seed of ops.sample_tokens: only a scheduler's graphs (``seeded``) read it
+        self.seed = torch.zeros(bp, dtype=torch.int64, device=dev)
+        self.seeded = False
+        self.min_p_on = False   # static batches: the sampled pick goes through ops.sample_tokens
         self.out = torch.zeros(bp, dtype=torch.long, device=dev)
         # penalties: the token ring of each slot (prompt + output; stream entry j at
         # hist[b, j % W]) and the per-slot parameters; only the penalised graphs touch them
@@ -328,7 +341,7 @@ class _DecodeGraph:
         g = cls.__new__(cls)
         g.bp = bp
         for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
-                     "top_k", "top_p", "out", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen",
+                     "top_k", "top_p", "min_p", "seed", "out", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen",
                      "lp_n", "lp", "lp_top_ids", "lp_top"):
             setattr(g, name, getattr(master, name)[:bp])
         g.shared_table, g.shared_len = master.shared_table, master.shared_len
@@ -339,6 +352,7 @@ class _DecodeGraph:
         g.cascade, g.greedy, g.graph = False, True, None
         g.penalized = False
         g.logprobs = False
+        g.seeded = g.min_p_on = False
         g.groups_fit = master.groups_fit
         g.hkv = master.hkv
         return g
@@ -431,6 +445,7 @@ class LLMEngine:
         cap = min(int(os.environ.get("DOCQA_TAIL_CACHE", "4096")), num_blocks // 8)
         self.tail = TailCache(self.kv.allocator, block_size, cap) if self._use_pc and cap > 0 else None
         self._graphs: dict[tuple, _DecodeGraph] = {}
+        self._graphs_min_p: dict[tuple, _DecodeGraph] = {}   # the static min_p flavours (_get_graph)
         self._pool = None
         self.stats = GenStats()
 
@@ -578,6 +593,16 @@ class LLMEngine:
         if g.greedy:
             return self.model.greedy(logits)
         src = self.model.full_logits(logits) if full is None else full
+        if g.seeded:
+            # a scheduler's graph: every row draws from its own (seed, position) stream, and the
+            # unpenalised rows' logits are read as the LM head wrote them
+            R = src.shape[0]    # the first-token pick covers the batch's rows, a step the bucket's
+            if g.penalized:
+                src = src.float().clone(memory_format=torch.contiguous_format)   # never the caller's logits
+                ops.apply_penalties(src, g.hist[:R], g.hist_n[:R], g.last_n[:R], g.rep_pen[:R], g.pres_pen[:R],
+                                    g.freq_pen[:R], g.valid[:R])
+            return ops.sample_tokens(src, self.cfg.vocab_size, g.inv_temp, g.top_k, g.top_p, g.min_p,
+                                     seed=g.seed, index=g.context_lens, valid=g.valid)
         full = src.float()
         if g.penalized:
             if not full.is_contiguous() or full.data_ptr() in (logits.data_ptr(), src.data_ptr()):
@@ -586,6 +611,8 @@ class LLMEngine:
             ops.apply_penalties(full, g.hist[:R], g.hist_n[:R], g.last_n[:R], g.rep_pen[:R], g.pres_pen[:R],
                                 g.freq_pen[:R], g.valid[:R])
         u = torch.rand(full.shape[0], device=full.device)
+        if g.min_p_on:
+            return ops.sample_tokens(full, self.cfg.vocab_size, g.inv_temp, g.top_k, g.top_p, g.min_p, u=u)
         return ops.sample(full, g.inv_temp, g.top_k, g.top_p, u)
 
     def _penalized_greedy(self, logits, g: _DecodeGraph, full=None):
@@ -617,18 +644,22 @@ class LLMEngine:
         return nxt
 
     def _get_graph(self, bp: int, greedy: bool, cascade: bool = False, fit: bool = True,
-                   penalized: bool = False, logprobs: bool = False) -> _DecodeGraph:
+                   penalized: bool = False, logprobs: bool = False, min_p: bool = False) -> _DecodeGraph:
+        """``min_p``: the sampled flavour whose pick is ops.sample_tokens -- graphs of their own
+        under the same key, so the key and the graphs without min_p stay what they were."""
         fit = fit or self.max_blocks_per_seq <= ops.GROUP_MAX_BLOCKS
         key = (bp, greedy, cascade, fit, penalized, logprobs)
-        g = self._graphs.get(key)
+        graphs = self._graphs_min_p if min_p else self._graphs
+        g = graphs.get(key)
         if g is None:
             g = _DecodeGraph(self, bp)
+            g.min_p_on = min_p
             g.greedy = greedy
             g.penalized = penalized
             g.logprobs = logprobs
             g.cascade = cascade
             g.groups_fit = fit
-            self._graphs[key] = g
+            graphs[key] = g
         return g
 
     def groups_fit(self, end_lens: list[int]) -> bool:
@@ -1010,7 +1041,7 @@ class LLMEngine:
             fit = self.groups_fit([n + params.max_new_tokens for n in lens])
             grouped = nshared > 0 or self.group_without_prefix(B, fit)
             g = self._get_graph(_bucket(B, self.max_batch) if self.use_graphs else B, greedy, grouped, fit,
-                                penalized, want_lp)
+                                penalized, want_lp, min_p=not greedy and params.min_p > 0)
             if grouped:
                 g.shared_len.fill_(0)
             if nshared:
@@ -1039,6 +1070,7 @@ class LLMEngine:
                 g.inv_temp.fill_(1.0 / params.temperature)
                 g.top_k.fill_(params.top_k)
                 g.top_p.fill_(params.top_p)
+                g.min_p.fill_(params.min_p)
                 if params.seed:
                     torch.manual_seed(params.seed)
             if want_lp:

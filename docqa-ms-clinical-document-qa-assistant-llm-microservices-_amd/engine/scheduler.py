@@ -51,6 +51,7 @@ import collections
 import concurrent.futures as cf
 import itertools
 import os
+import random
 import threading
 import time
 from dataclasses import dataclass, field
@@ -89,6 +90,19 @@ class Request:
     pos: int = 0
     preemptions: int = 0
     filled: int = 0      # mixed steps: prompt tokens already in the KV cache
+    # key of the request's sampling stream (ops.seeded_uniform): params.seed, or a random one of
+    # its own drawn at submission -- never written back to ``params``, which callers share
+    seed: int = 0
+
+
+_SEED_RNG = random.SystemRandom()
+
+
+def request_seed(params: SamplingParams) -> int:
+    """``params.seed`` as the int64 a slot's seed buffer holds, or, when it is unset (0), a fresh
+    non-zero 63-bit one."""
+    s = ((int(params.seed) + (1 << 63)) % (1 << 64)) - (1 << 63)
+    return s or (_SEED_RNG.getrandbits(63) or 1)
 
 
 class Lockstep:
@@ -97,9 +111,11 @@ class Lockstep:
     timing-dependent admission decision; before every engine step it broadcasts the
     requests that arrived since the last step and that decision over a CPU (gloo) group.
     Everything else a step does -- KV reservation, prefix-cache hits, prefill, decode,
-    retirement on EOS -- is a deterministic function of that input and of the greedy ids,
-    which the vocab-parallel argmax makes identical on every rank, so the followers' TP
-    forwards always match the leader's.  While idle the leader sends a heartbeat every
+    retirement on EOS -- is a deterministic function of that input and of the picked ids:
+    the vocab-parallel argmax makes the greedy ones identical on every rank, and a sampled
+    request's seed (the leader draws one for an unseeded request) travels with it, so every
+    rank draws the same counter-based stream.  The followers' TP forwards therefore always
+    match the leader's.  While idle the leader sends a heartbeat every
     ``heartbeat_s`` so the followers' receive never times out."""
 
     def __init__(self, group, src: int, leader: bool, heartbeat_s: float = 1.0):
@@ -195,7 +211,7 @@ class ContinuousEngine:
             # (the API layer truncates the text at the stop string all the same)
             stop_check = None
         r = Request(next(self._ids), list(prompt), params, fut, on_token, stop_check,
-                    t_arrival=time.perf_counter())
+                    t_arrival=time.perf_counter(), seed=request_seed(params))
         fut.request = r      # the caller reads r.logprobs (parallel to the result) off the future
         with self._cv:
             # a lockstep leader queues arrivals for the next step's broadcast, so the
@@ -324,7 +340,7 @@ class ContinuousEngine:
                 self.waiting.extend(new)
             decision = self._admission_due()
             try:
-                self.lockstep.exchange(("step", [(r.prompt, r.params) for r in new], decision))
+                self.lockstep.exchange(("step", [(r.prompt, r.params, r.seed) for r in new], decision))
             except Exception as e:  # noqa: BLE001 - a follower is gone: the TP group is broken
                 raise CollectiveError(f"lockstep broadcast failed: {e!r}") from e
         self._step(decision)
@@ -368,9 +384,9 @@ class ContinuousEngine:
             if msg[0] != "step":
                 continue
             _, specs, decision = msg
-            for prompt, params in specs:
+            for prompt, params, seed in specs:
                 self.waiting.append(Request(next(self._ids), list(prompt), params, cf.Future(),
-                                            t_arrival=time.perf_counter()))
+                                            t_arrival=time.perf_counter(), seed=seed))
             try:
                 self._step(decision)
             except Exception as e:  # noqa: BLE001
@@ -469,8 +485,7 @@ class ContinuousEngine:
                                    greedy=greedy)
                 err = comm.collective_error_snapshot()
                 first_lp: list = [None] * len(adm)
-                first = out.tolist() if greedy else self._sample_rows(out, [r.params for r in adm],
-                                                                          [self._stream(r) for r in adm], first_lp)
+                first = out.tolist() if greedy else self._sample_rows(out, adm, first_lp)
                 comm.raise_on_collective_error(err)
         except CollectiveError:
             for r in adm:
@@ -684,6 +699,8 @@ class ContinuousEngine:
         it = torch.ones(k, dtype=torch.float32)
         tk = torch.zeros(k, dtype=torch.int32)
         tp = torch.ones(k, dtype=torch.float32)
+        mp = torch.zeros(k, dtype=torch.float32)
+        sd = torch.tensor([r.seed for r in reqs], dtype=torch.int64)
         # penalties: the ring is the tail of the request's stream so far, first token included
         W = ops.PENALTY_WINDOW
         hist = torch.zeros(k, W, dtype=torch.int32)
@@ -705,6 +722,7 @@ class ContinuousEngine:
             pos[i] = r.pos
             if r.params.temperature > 0:
                 it[i], tk[i], tp[i] = 1.0 / r.params.temperature, r.params.top_k, r.params.top_p
+                mp[i] = r.params.min_p
             else:
                 tk[i] = 1                        # greedy row inside a sampled batch: argmax
         dev = m.tokens.device
@@ -717,6 +735,8 @@ class ContinuousEngine:
         m.inv_temp[sl].copy_(it.to(dev, non_blocking=True))
         m.top_k[sl].copy_(tk.to(dev, non_blocking=True))
         m.top_p[sl].copy_(tp.to(dev, non_blocking=True))
+        m.min_p[sl].copy_(mp.to(dev, non_blocking=True))
+        m.seed[sl].copy_(sd.to(dev, non_blocking=True))
         m.hist[sl].copy_(hist.to(dev, non_blocking=True))
         m.hist_n[sl].copy_(hn.to(dev, non_blocking=True))
         m.last_n[sl].copy_(ln.to(dev, non_blocking=True))
@@ -733,16 +753,16 @@ class ContinuousEngine:
         output tokens: only the original prompt counts)."""
         return r.prompt[:r.orig_len if r.orig_len >= 0 else len(r.prompt)] + r.out
 
-    def _sample_rows(self, logits: torch.Tensor, params: list[SamplingParams],
-                     streams: list[list[int]] | None = None, lp_out: list | None = None) -> list[int]:
-        """First tokens of admitted requests from their prefill logits; ``streams``: each
-        request's tokens so far, the penalty window of the penalised ones.  ``lp_out``: a list
-        with one slot per request that receives the first token's (logprob, top list) of the
-        requests that ask for logprobs, from these logits as the LM head wrote them."""
+    def _sample_rows(self, logits: torch.Tensor, reqs: list[Request], lp_out: list | None = None) -> list[int]:
+        """First tokens of admitted requests from their prefill logits (the penalised ones under
+        the penalty window of their tokens so far).  ``lp_out``: a list with one slot per request
+        that receives the first token's (logprob, top list) of the requests that ask for
+        logprobs, from these logits as the LM head wrote them."""
+        params = [r.params for r in reqs]
         if lp_out is None or not any(p.logprobs for p in params):
-            return self._pick_rows(logits, params, streams)
+            return self._pick_rows(logits, reqs)
         # the penalised greedy pick clobbers its input: it gets a copy, the logprobs the original
-        ids = self._pick_rows(logits, params, streams, keep=True)
+        ids = self._pick_rows(logits, reqs, keep=True)
         full = self.eng.model.full_logits(logits)
         dev = full.device
         lp, ti, tl = ops.token_logprobs(full, self.eng.cfg.vocab_size, torch.tensor(ids, dtype=torch.long, device=dev),
@@ -753,10 +773,12 @@ class ContinuousEngine:
                 lp_out[i] = logprob_entry(lp[i], ti[i], tl[i])
         return ids
 
-    def _pick_rows(self, logits: torch.Tensor, params: list[SamplingParams],
-                   streams: list[list[int]] | None = None, keep: bool = False) -> list[int]:
-        """The pick of :meth:`_sample_rows`; ``keep``: ``logits`` must survive it unchanged."""
+    def _pick_rows(self, logits: torch.Tensor, reqs: list[Request], keep: bool = False) -> list[int]:
+        """The pick of :meth:`_sample_rows`; ``keep``: ``logits`` must survive it unchanged.  A
+        sampled row draws at index len(prompt), the absolute position of its first token (a
+        resumed request's prompt already holds its earlier output), from the request's seed."""
         model = self.eng.model
+        params = [r.params for r in reqs]
         if all(p.temperature <= 0.0 and p.neutral for p in params):
             # greedy neutral rows (with logprobs: the argmax of the logits they come from)
             return model.greedy(logits).tolist()
@@ -765,7 +787,7 @@ class ContinuousEngine:
         pen = None
         if not all(p.neutral for p in params):
             W = ops.PENALTY_WINDOW
-            rings = [ring_of(s if not p.neutral else [], W) for p, s in zip(params, streams)]
+            rings = [ring_of(self._stream(r) if not r.params.neutral else [], W) for r in reqs]
             pen = (torch.stack([h for h, _ in rings]).to(dev),
                    torch.tensor([n for _, n in rings], dtype=torch.int32, device=dev),
                    torch.tensor([p.repeat_last_n for p in params], dtype=torch.int32, device=dev),
@@ -774,16 +796,17 @@ class ContinuousEngine:
                    torch.tensor([p.frequency_penalty for p in params], dtype=torch.float32, device=dev))
             if all(p.temperature <= 0 for p in params):
                 return ops.penalized_argmax(full.clone() if keep else full, full.shape[1], *pen).tolist()
-        if pen is not None and (full.dtype == torch.float32):
-            full = full.clone(memory_format=torch.contiguous_format)
-        full = full.float()
-        if pen is not None:
+            # penalised sampled rows: the penalties need an fp32 copy, which the sampler then reads
+            full = full.float().clone(memory_format=torch.contiguous_format) if full.dtype == torch.float32 \
+                else full.float()
             ops.apply_penalties(full, *pen)
         it = torch.tensor([1.0 / p.temperature if p.temperature > 0 else 1.0 for p in params], device=dev)
         tk = torch.tensor([p.top_k if p.temperature > 0 else 1 for p in params], dtype=torch.int32, device=dev)
         tp = torch.tensor([p.top_p if p.temperature > 0 else 1.0 for p in params], device=dev)
-        u = torch.rand(full.shape[0], device=dev)
-        return ops.sample(full, it, tk, tp, u).tolist()
+        mp = torch.tensor([p.min_p if p.temperature > 0 else 0.0 for p in params], device=dev)
+        seed = torch.tensor([r.seed for r in reqs], dtype=torch.int64, device=dev)
+        index = torch.tensor([len(r.prompt) for r in reqs], dtype=torch.int32, device=dev)
+        return ops.sample_tokens(full, self.eng.cfg.vocab_size, it, tk, tp, mp, seed=seed, index=index).tolist()
 
     def _graph(self, bp: int, greedy: bool, cascade: bool, fit: bool = True,
                penalized: bool = False, logprobs: bool = False) -> _DecodeGraph:
@@ -795,6 +818,7 @@ class ContinuousEngine:
             g.greedy, g.cascade, g.groups_fit = greedy, cascade, fit
             g.penalized = penalized
             g.logprobs = logprobs
+            g.seeded = True      # this scheduler's graphs sample per slot from (seed, position)
             self._graphs[key] = g
         return g
 
@@ -1021,7 +1045,7 @@ class ContinuousEngine:
         if keep != list(range(k)):
             idx = torch.tensor(keep, dtype=torch.long, device=m.tokens.device)
             for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
-                         "top_k", "top_p", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen", "lp_n"):
+                         "top_k", "top_p", "min_p", "seed", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen", "lp_n"):
                 t = getattr(m, name)
                 t[:k] = t[idx]
         m.lp_n[k:n].fill_(-1)

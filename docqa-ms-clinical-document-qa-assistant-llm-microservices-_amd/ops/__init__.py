@@ -1390,6 +1390,44 @@ def sample(logits, inv_temp, top_k, top_p, u):
     return ref.sample(logits, inv_temp, top_k, top_p, u)
 
 
+def seeded_uniform(seed, index):
+    """Counter-based uniforms: fp32 [R] in [0, 1) from ``seed`` int64 [R] and ``index`` int32 [R].
+    Philox4x32-10 with key ``(seed & 0xffffffff, seed >> 32)`` and counter ``(index, 0, 0, 0)``;
+    of the first output word ``w0``, ``u = float(w0 >> 8) * 2^-24`` (exact in fp32, at most
+    ``1 - 2^-24``).  ``index`` is the absolute position, in prompt + output, of the token the
+    uniform draws, so a request's stream depends on its seed alone: not on its slot, its
+    neighbours, a preemption or the process's generator.  GPU and CPU agree bit for bit."""
+    if _gpu(seed):
+        return _native().seeded_uniform(seed.contiguous(), index.contiguous())
+    return ref.seeded_uniform(seed, index)
+
+
+def sample_tokens(logits, n_valid: int, inv_temp, top_k, top_p, min_p, *, u=None, seed=None, index=None,
+                  valid=None):
+    """One token id per row (int64 [R]) of ``logits`` [R, ld], bf16 or fp32, read as they are --
+    on a GPU once, with no fp32 copy (csrc/kernels/sample.hip); columns at or past ``n_valid``
+    take no part.  Any row stride and alignment is served: bf16 rows that the 16-byte loads cannot
+    take (``ld % 8``, a misaligned base, more than 131072 columns) and fp32 rows run the same
+    code over memory.
+
+    Temperature, top-k, top-p and the draw are the contract of :func:`sample` with
+    ``x = float32(logit) * inv_temp``: ties at a cutoff are all kept, ``top_k == 1`` is the lowest
+    index of the maximum whatever the other parameters are, and the draw is the inverse CDF of the
+    kept tokens in index order.  ``min_p`` (fp32 [R], or None): ``0 < min_p <= 1`` keeps, in
+    addition, only ``x >= max(x) + log(min_p)``, i.e. ``p_i >= min_p * p_max`` -- a ratio no
+    other filter changes, as the maximum survives them all; ``min_p <= 0`` is off.
+
+    The row's uniform is exactly one of ``u`` (fp32 [R], the caller's) and ``seed`` int64 [R] +
+    ``index`` int32 [R] (:func:`seeded_uniform`, computed inside the kernel).  Rows with
+    ``valid == 0`` (int32 [R], padding slots) write token 0 and read nothing.  Per-row tensors
+    are contiguous, on the logits' device and at least R long."""
+    if (u is None) == (seed is None) or (seed is None) != (index is None):
+        raise ValueError("sample_tokens: exactly one of u and seed + index")
+    if _gpu(logits):
+        return _native().sample_tokens(logits, int(n_valid), inv_temp, top_k, top_p, min_p, u, seed, index, valid)
+    return ref.sample_tokens(logits, int(n_valid), inv_temp, top_k, top_p, min_p, u, seed, index, valid)
+
+
 PENALTY_WINDOW = ref.PENALTY_WINDOW   # capacity W of the per-slot token ring hist [B, W]
 
 

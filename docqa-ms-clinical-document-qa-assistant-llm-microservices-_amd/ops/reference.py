@@ -299,6 +299,72 @@ def sample(logits, inv_temp, top_k, top_p, u):
     return out
 
 
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32(counter, key, rounds: int = 10):
+    """Philox4x32 (Salmon et al., Random123) in Python integers: ``counter`` four and ``key`` two
+    32-bit words -> the four output words."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+    k0, k1 = (int(k) & _M32 for k in key)
+    for _ in range(rounds):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def seeded_uniform(seed, index):
+    """fp32 [R] in [0, 1): the first word of philox4x32 with key (seed & 0xffffffff, seed >> 32)
+    and counter (index, 0, 0, 0), as ``float(w0 >> 8) * 2^-24`` -- exact in fp32, at most
+    1 - 2^-24.  Integer arithmetic throughout: the device kernel agrees bit for bit."""
+    out = torch.empty(len(seed), dtype=torch.float32)
+    for r, (s, i) in enumerate(zip(seed.tolist(), index.tolist())):
+        s &= 0xFFFFFFFFFFFFFFFF
+        w0 = philox4x32((i, 0, 0, 0), (s & _M32, s >> 32))[0]
+        out[r] = (w0 >> 8) * 2.0 ** -24
+    return out.to(seed.device)
+
+
+def sample_tokens(logits, n_valid, inv_temp, top_k, top_p, min_p, u=None, seed=None, index=None, valid=None):
+    """:func:`sample` over the columns below ``n_valid`` plus the ``min_p`` filter
+    (``x >= max(x) + log(min_p)``, in fp32 like the kernel), the row's uniform either ``u`` or
+    :func:`seeded_uniform`; rows with ``valid == 0`` get token 0."""
+    R = logits.shape[0]
+    if u is None:
+        u = seeded_uniform(seed[:R], index[:R])
+    out = torch.zeros(R, dtype=torch.long, device=logits.device)
+    for r in range(R):
+        if valid is not None and int(valid[r]) == 0:
+            continue
+        x = logits[r, :n_valid].float() * inv_temp[r].float()
+        k = int(top_k[r])
+        if k == 1:      # greedy row: the lowest index of the maximum, whatever else is set
+            out[r] = int(torch.nonzero(x == x.max())[0])
+            continue
+        keep = torch.ones_like(x, dtype=torch.bool)
+        if 0 < k < x.numel():
+            keep = x >= torch.topk(x, k).values[-1]
+        p = torch.softmax(torch.where(keep, x, torch.full_like(x, -math.inf)), -1)
+        tp = float(top_p[r])
+        if 0.0 < tp < 1.0:
+            sx = torch.sort(torch.where(keep, x, torch.full_like(x, -math.inf)), descending=True).values
+            sp = torch.softmax(sx, -1)
+            n = int((torch.cumsum(sp, 0) - sp < tp).sum())      # the prefix; then its ties
+            keep = keep & (x >= sx[n - 1])
+        mp = float(min_p[r]) if min_p is not None else 0.0
+        if mp > 0.0:
+            keep = keep & (x >= x.max() + torch.log(torch.tensor(min(mp, 1.0), dtype=torch.float32)))
+        p = torch.where(keep, p, torch.zeros_like(p))
+        p = p / p.sum()
+        c = torch.cumsum(p, 0)
+        idx = int(torch.searchsorted(c, torch.tensor([float(u[r])], device=c.device), right=True))
+        out[r] = min(idx, int(torch.nonzero(p > 0)[-1]))
+    return out
+
+
 def paged_decode(q, k_cache, v_cache, block_tables, context_lens, Hq, max_context, scale):
     B = q.shape[0]
     NB, Hkv, BS, D = k_cache.shape

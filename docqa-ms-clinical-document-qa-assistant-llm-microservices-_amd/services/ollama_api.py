@@ -9,8 +9,8 @@ service's URL gets its completions from the MI355X engine (continuous batching w
 other request in flight) instead of a llama.cpp process.
 
   POST /api/chat      {"model", "messages": [{"role", "content"}], "stream" (default true),
-                       "options": {"temperature", "num_predict", "top_k", "top_p", "seed",
-                                   "repeat_penalty", "repeat_last_n", "presence_penalty",
+                       "options": {"temperature", "num_predict", "top_k", "top_p", "min_p",
+                                   "seed", "repeat_penalty", "repeat_last_n", "presence_penalty",
                                    "frequency_penalty", "stop"},
                        "logprobs" (default false), "top_logprobs" (0..20)}
                       -> {"model", "created_at", "message": {"role": "assistant", "content"},
@@ -42,6 +42,16 @@ REPEAT_LAST_N / PRESENCE_PENALTY / FREQUENCY_PENALTY rather than Ollama's 1.1 ov
 (docs/CONFIG.md); "format", "keep_alive", "images" and "tools" are ignored.  "stop" (a string
 or a list) ends the text just before the earliest match with done_reason "stop"; a streamed
 tail that could still grow into a stop string is held back until it is resolved.
+Temperature comes FIRST: top_k, top_p and min_p filter the distribution at the request's
+temperature (x = logit / temperature), where llama.cpp's default sampler chain applies the
+temperature after those filters.  top_k does not notice; a top_p or min_p cutoff at
+temperature != 1 keeps a different set than llama.cpp would.  "min_p" (0..1, default 0: off)
+keeps the tokens with p >= min_p * p_max; a value outside [0, 1] is a 400 {"error"}.
+"seed": on the continuous scheduler a sampled request (temperature > 0) with a non-zero seed
+returns the same completion for the same prompt, options and seed, whatever else is in flight,
+at any TP degree: each token is drawn from a counter-based stream keyed by (seed, position)
+(ops.seeded_uniform).  Seed 0 or none: a fresh random seed per request.  The static batcher
+(DOCQA_SERVING=static) reproduces per batch only.
 Durations are nanoseconds like Ollama's.  Streaming is token by token on the continuous
 scheduler (DOCQA_SERVING=continuous, the default); the static batcher returns the whole
 completion as one piece.
@@ -93,14 +103,18 @@ def _now() -> str:
 
 def sampling_from_options(options: dict | None, settings, max_context: int, prompt_len: int) -> SamplingParams:
     """Ollama ``options`` -> SamplingParams: num_predict (-1 / -2: up to the context) caps
-    the new tokens, temperature 0 is greedy; the penalties default to the service settings."""
+    the new tokens, temperature 0 is greedy; the penalties default to the service settings.
+    Raises ValueError (the routes answer 400) on a ``min_p`` outside [0, 1]."""
     o = options or {}
     n = int(o.get("num_predict", settings.max_new_tokens))
     room = max(1, max_context - prompt_len)
     n = room if n < 0 else max(1, min(n, room))
+    min_p = float(o.get("min_p", 0.0) or 0.0)
+    if not 0.0 <= min_p <= 1.0:      # also refuses NaN
+        raise ValueError("min_p must be between 0 and 1")
     return SamplingParams(max_new_tokens=n, temperature=float(o.get("temperature", settings.temperature)),
                           top_k=int(o.get("top_k", 0) or 0), top_p=float(o.get("top_p", 1.0) or 1.0),
-                          stop_on_eos=True, seed=int(o.get("seed", 0) or 0),
+                          min_p=min_p, stop_on_eos=True, seed=int(o.get("seed", 0) or 0),
                           repeat_penalty=float(_opt(o, "repeat_penalty", settings.repeat_penalty)),
                           repeat_last_n=int(_opt(o, "repeat_last_n", settings.repeat_last_n)),
                           presence_penalty=float(_opt(o, "presence_penalty", settings.presence_penalty)),
@@ -192,7 +206,10 @@ def register(app: FastAPI, settings, metrics) -> None:
             return JSONResponse(status_code=400, content={"error": bad})
         tok = pipe.chat_tok
         ids = _prompt_ids(pipe, ids)
-        params = sampling_from_options(options, settings, pipe.engine.max_context, len(ids))
+        try:
+            params = sampling_from_options(options, settings, pipe.engine.max_context, len(ids))
+        except ValueError as e:
+            return JSONResponse(status_code=400, content={"error": str(e)})
         params.logprobs, params.top_logprobs = bool(logprobs), int(top_logprobs)
         metrics.inc(f"ollama_{kind}_requests")
         loop = asyncio.get_running_loop()
