@@ -606,6 +606,70 @@ void token_logprobs(const at::Tensor& logits, int64_t n_valid, const at::Tensor&
                                 top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), stream()), "token_logprobs");
 }
 
+// grammar-constrained decoding: the shared checks of the vocabulary-bytes table and the lexer table
+static void check_grammar(const char* op, const at::Tensor& ref, int64_t R, const at::Tensor& state,
+                          const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& table,
+                          const c10::optional<at::Tensor>& valid) {
+  const auto on_dev = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == ref.device(); };
+  TORCH_CHECK(on_dev(state) && on_dev(tok_off) && on_dev(tok_bytes) && on_dev(table), op,
+              ": every tensor on one device");
+  TORCH_CHECK(state.scalar_type() == at::kLong && state.is_contiguous() && state.numel() == R, op,
+              ": state must be contiguous int64 [rows]");
+  TORCH_CHECK(tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.numel() >= 1, op,
+              ": tok_off must be contiguous int32 [V + 1]");
+  TORCH_CHECK(tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
+                  tok_bytes.numel() < (int64_t(1) << 31), op, ": tok_bytes must be contiguous uint8");
+  TORCH_CHECK(table.scalar_type() == at::kShort && table.is_contiguous() && table.dim() == 2 &&
+                  table.size(1) == 256 && table.size(0) >= 1 && table.size(0) <= docqa_grammar_max_states(),
+              op, ": table must be contiguous int16 [states <= ", docqa_grammar_max_states(), ", 256]");
+  CHECK_ALIGN16(table);
+  if (valid.has_value() && valid->defined())
+    TORCH_CHECK(on_dev(*valid) && valid->scalar_type() == at::kInt && valid->is_contiguous() &&
+                    valid->numel() >= R, op, ": valid must be contiguous int32 [>= rows]");
+}
+
+// in place: -inf into every column t < n_valid of a constrained row (state != 0, valid != 0)
+// whose token the row's automaton state does not allow; nothing else is written
+void grammar_mask(at::Tensor logits, int64_t n_valid, const at::Tensor& state, const at::Tensor& tok_off,
+                  const at::Tensor& tok_bytes, const at::Tensor& table, int64_t eos_id,
+                  const c10::optional<at::Tensor>& valid) {
+  CHECK_GPU(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "grammar_mask wants [rows, V] with unit stride");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "grammar_mask: bf16 or fp32 logits");
+  const int64_t R = logits.size(0), V = logits.size(1), ld = logits.stride(0);
+  TORCH_CHECK(n_valid >= 1 && n_valid <= V, "grammar_mask: n_valid must be in [1, V]");
+  TORCH_CHECK(R <= 1 || ld >= V, "grammar_mask: row stride below V");
+  TORCH_CHECK(R <= 65535, "grammar_mask: at most 65535 rows");
+  check_grammar("grammar_mask", logits, R, state, tok_off, tok_bytes, table, valid);
+  if (R == 0) return;
+  c10::DeviceGuard g(logits.device());
+  CHECK_RC(docqa_grammar_mask(logits.data_ptr(), (int)R, (int)n_valid, (long)ld, bf ? 1 : 0,
+                              state.data_ptr<int64_t>(), valid_ptr(valid), tok_off.data_ptr<int>(),
+                              (int)tok_off.numel() - 1, tok_bytes.numel() ? tok_bytes.data_ptr<uint8_t>() : nullptr,
+                              (int)tok_bytes.numel(), table.data_ptr(), (int)table.size(0), (int)eos_id, stream()),
+           "grammar_mask");
+}
+
+// in place: state[i] <- the automaton after the bytes of token nxt[i] (0, DONE, EOS and a token
+// that would be rejected leave it as it is)
+void grammar_advance(at::Tensor state, const at::Tensor& nxt, const at::Tensor& tok_off,
+                     const at::Tensor& tok_bytes, const at::Tensor& table, int64_t eos_id,
+                     const c10::optional<at::Tensor>& valid) {
+  CHECK_GPU(state);
+  const int64_t R = state.numel();
+  TORCH_CHECK(nxt.is_cuda() && nxt.device() == state.device() && nxt.scalar_type() == at::kLong &&
+                  nxt.is_contiguous() && nxt.numel() == R, "grammar_advance: nxt must be contiguous int64 [rows]");
+  check_grammar("grammar_advance", state, R, state, tok_off, tok_bytes, table, valid);
+  if (R == 0) return;
+  c10::DeviceGuard g(state.device());
+  CHECK_RC(docqa_grammar_advance(state.data_ptr<int64_t>(), nxt.data_ptr<int64_t>(), (int)R, valid_ptr(valid),
+                                 tok_off.data_ptr<int>(), (int)tok_off.numel() - 1,
+                                 tok_bytes.numel() ? tok_bytes.data_ptr<uint8_t>() : nullptr,
+                                 (int)tok_bytes.numel(), table.data_ptr(), (int)table.size(0), (int)eos_id,
+                                 stream()), "grammar_advance");
+}
+
 // decode_advance + the ring: hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1 for valid rows
 void decode_advance_hist(const at::Tensor& nxt, at::Tensor out, at::Tensor tokens, at::Tensor positions,
                          at::Tensor context_lens, const at::Tensor& valid, at::Tensor hist,
@@ -1924,6 +1988,10 @@ TORCH_LIBRARY(docqa, m) {
         "Tensor pres_pen, Tensor freq_pen, Tensor? valid=None) -> ()");
   m.def("penalized_argmax(Tensor(a!) logits, int n_valid, Tensor hist, Tensor hist_n, Tensor last_n, "
         "Tensor rep_pen, Tensor pres_pen, Tensor freq_pen, Tensor? valid=None) -> Tensor");
+  m.def("grammar_mask(Tensor(a!) logits, int n_valid, Tensor state, Tensor tok_off, Tensor tok_bytes, "
+        "Tensor table, int eos_id, Tensor? valid=None) -> ()");
+  m.def("grammar_advance(Tensor(a!) state, Tensor nxt, Tensor tok_off, Tensor tok_bytes, Tensor table, "
+        "int eos_id, Tensor? valid=None) -> ()");
   m.def("top_logprobs_max() -> int", &top_logprobs_max);
   m.def("token_logprobs(Tensor logits, int n_valid, Tensor chosen, Tensor top_n, Tensor(a!) lp, "
         "Tensor(b!) top_ids, Tensor(c!) top_lp) -> ()");
@@ -2044,6 +2112,8 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("sample_tokens", &sample_tokens);
   m.impl("apply_penalties", &apply_penalties);
   m.impl("penalized_argmax", &penalized_argmax);
+  m.impl("grammar_mask", &grammar_mask);
+  m.impl("grammar_advance", &grammar_advance);
   m.impl("token_logprobs", &token_logprobs);
   m.impl("decode_advance_hist", &decode_advance_hist);
   m.impl("paged_decode", &paged_decode);

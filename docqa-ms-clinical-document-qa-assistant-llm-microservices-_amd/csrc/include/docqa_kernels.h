@@ -99,6 +99,19 @@ int docqa_token_logprobs(const void* logits, int rows, int n_valid, int ld, int 
                          const int* top_n, float* pm, float* ps, float* ptv, int* pti, float* lp, int* top_ids,
                          float* top_lp, hipStream_t s);
 
+// grammar-constrained decoding (grammar.hip): per-row automaton state words (0: unconstrained),
+// the vocabulary's bytes as tok_off int32 [n_tok + 1] into tok_bytes [total] and the lexer table
+// int16 [n_states <= docqa_grammar_max_states(), 256].  mask: -inf into the logits of tokens a
+// row's state does not allow (columns < n_valid; EOS only in DONE); advance: the state after the
+// picked token.  valid may be null (all rows).
+int docqa_grammar_max_states();
+int docqa_grammar_mask(void* logits, int rows, int n_valid, long ld, int is_bf16, const int64_t* state,
+                       const int* valid, const int* tok_off, int n_tok, const uint8_t* tok_bytes, int total,
+                       const void* table, int n_states, int eos_id, hipStream_t s);
+int docqa_grammar_advance(int64_t* state, const int64_t* nxt, int rows, const int* valid, const int* tok_off,
+                          int n_tok, const uint8_t* tok_bytes, int total, const void* table, int n_states,
+                          int eos_id, hipStream_t s);
+
 int docqa_paged_decode(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                        const int* block_tables, int maxb, const int* context_lens, void* out,
                        int out_stride, float* tmp_out, float* tmp_ml, int B, int Hq, int Hkv,

@@ -69,9 +69,20 @@ class SamplingParams:
     # (0..ops.TOP_LOGPROBS_MAX, clamped) most likely tokens'
     logprobs: bool = False
     top_logprobs: int = 0
+    # "json": grammar-constrained decoding -- the output is a prefix of ONE JSON object
+    # (ops.grammar: whitespace runs <= 16, nesting <= 32), EOS allowed only once it has closed;
+    # "" is off.  Needs the vocabulary's bytes on the engine (LLMEngine.set_vocab_bytes).
+    format: str = ""
 
     def __post_init__(self):
         self.top_logprobs = max(0, min(int(self.top_logprobs), ops.TOP_LOGPROBS_MAX))
+        if self.format not in ("", "json"):
+            raise ValueError(f'format must be "" or "json", got {self.format!r}')
+
+    @property
+    def constrained(self) -> bool:
+        """The request's tokens are masked by the JSON automaton."""
+        return self.format == "json"
 
     @property
     def neutral(self) -> bool:
@@ -81,9 +92,9 @@ class SamplingParams:
 
     @property
     def fused_greedy_ok(self) -> bool:
-        """Greedy, neutral and no logprobs: the LM head's fused argmax picks the token (it
-        never writes the logits the logprobs are taken from)."""
-        return self.temperature <= 0.0 and self.neutral and not self.logprobs
+        """Greedy, neutral, no logprobs and unconstrained: the LM head's fused argmax picks the
+        token (it never writes the logits the logprobs are taken from or the grammar masks)."""
+        return self.temperature <= 0.0 and self.neutral and not self.logprobs and not self.constrained
 
     @property
     def lp_n(self) -> int:
@@ -314,6 +325,10 @@ class _DecodeGraph:
         self.lp_top_ids = torch.full((bp, ops.TOP_LOGPROBS_MAX), -1, dtype=torch.int32, device=dev)
         self.lp_top = torch.full((bp, ops.TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=dev)
         self.logprobs = False
+        # grammar-constrained decoding: each slot's automaton state (ops.grammar; 0: the slot is
+        # not constrained); only the constrained graphs touch it
+        self.gstate = torch.zeros(bp, dtype=torch.int64, device=dev)
+        self.constrained = False
         # cascade decode: block ids / length of the prompt prefix every row shares
         self.shared_table = torch.zeros(eng.max_blocks_per_seq, dtype=torch.int32, device=dev)
         self.shared_len = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -342,7 +357,7 @@ class _DecodeGraph:
         g.bp = bp
         for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
                      "top_k", "top_p", "min_p", "seed", "out", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen",
-                     "lp_n", "lp", "lp_top_ids", "lp_top"):
+                     "lp_n", "lp", "lp_top_ids", "lp_top", "gstate"):
             setattr(g, name, getattr(master, name)[:bp])
         g.shared_table, g.shared_len = master.shared_table, master.shared_len
         g.order = torch.arange(bp, dtype=torch.int32, device=master.tokens.device)
@@ -352,6 +367,7 @@ class _DecodeGraph:
         g.cascade, g.greedy, g.graph = False, True, None
         g.penalized = False
         g.logprobs = False
+        g.constrained = False
         g.seeded = g.min_p_on = False
         g.groups_fit = master.groups_fit
         g.hkv = master.hkv
@@ -446,6 +462,10 @@ class LLMEngine:
         self.tail = TailCache(self.kv.allocator, block_size, cap) if self._use_pc and cap > 0 else None
         self._graphs: dict[tuple, _DecodeGraph] = {}
         self._graphs_min_p: dict[tuple, _DecodeGraph] = {}   # the static min_p flavours (_get_graph)
+        self._graphs_json: dict[tuple, _DecodeGraph] = {}    # the static constrained flavours
+        # grammar-constrained decoding: the vocabulary's bytes (set_vocab_bytes)
+        self.vocab_bytes: list | None = None
+        self._grammar = None      # (tok_off int32 [V + 1], tok_bytes uint8, table int16) on the device
         self._pool = None
         self.stats = GenStats()
 
@@ -535,6 +555,15 @@ class LLMEngine:
     # ------------------------------------------------------------------ decode step
     def _step_body(self, g: _DecodeGraph) -> None:
         meta = self._decode_meta(g)
+        if g.constrained:
+            # constrained flavours: [B, vocab] logits, the grammar mask in front of the flavour's
+            # pick, and every slot's automaton advances by its token inside the step
+            nxt = self._pick_constrained(self.model.forward(g.tokens, meta, self.kv.caches), g)
+            if g.penalized:
+                ops.decode_advance_hist(nxt, g.out, g.tokens, g.positions, g.context_lens, g.valid, g.hist, g.hist_n)
+            else:
+                ops.decode_advance(nxt, g.out, g.tokens, g.positions, g.context_lens, g.valid)
+            return
         if g.logprobs:
             # logprob flavours: [B, vocab] logits, the slots' logprobs from them, and the pick
             # the flavour has anyway (a greedy neutral row: the argmax of these very logits)
@@ -643,16 +672,79 @@ class LLMEngine:
                            g.lp_top_ids[:R], g.lp_top[:R])
         return nxt
 
+    # ------------------------------------------------------------------ format: "json"
+    def set_vocab_bytes(self, token_bytes: list) -> None:
+        """The raw bytes of every token id (``ChatTokenizer.token_bytes(vocab_size)``; ``b""``:
+        special or unknown, never allowed in a constrained row), uploaded once with the JSON
+        automaton's table.  Constrained requests (``SamplingParams.format``) need it.  Raises
+        ValueError if a single-byte token is missing (ops.grammar.vocab_tensors)."""
+        from ..ops import grammar
+
+        token_bytes = list(token_bytes)[:self.cfg.vocab_size]
+        off, data = grammar.vocab_tensors(token_bytes)
+        self._grammar = tuple(t.to(self.device) for t in (off, data, grammar.table()))
+        self.vocab_bytes = token_bytes
+
+    def require_grammar(self, params: SamplingParams) -> None:
+        if params.constrained and self._grammar is None:
+            raise ValueError('format "json" needs the vocabulary bytes: LLMEngine.set_vocab_bytes(...) was not called')
+
+    def grammar_state(self, out: list) -> int:
+        """The automaton state of a constrained request that has emitted ``out`` (replayed
+        through the host walk, which the kernels match as int64)."""
+        from ..ops import grammar
+
+        return grammar.replay(out, self.vocab_bytes, self.cfg.eos_token_id)
+
+    def _pick_constrained(self, logits, g: _DecodeGraph):
+        """The constrained flavours' pick from ``logits`` (the LM head's, a vocab shard at TP > 1):
+        the rows' grammar mask over the gathered logits, the flavour's pick on the masked rows
+        (greedy: ops.argmax / ops.penalized_argmax; sampled: always ops.sample_tokens, whose
+        contract covers -inf), the logprobs -- the model's own distribution -- from a copy taken
+        BEFORE the mask, then the rows' automata advance by their token.  Rows with state 0 pass
+        both grammar kernels untouched.  Returns int64 [R] contiguous."""
+        V, eos = self.cfg.vocab_size, self.cfg.eos_token_id
+        off, data, table = self._grammar
+        full = self.model.full_logits(logits)
+        R = full.shape[0]   # the first-token pick covers the batch's rows, a step the bucket's
+        raw = full.clone() if g.logprobs else None
+        ops.grammar_mask(full, V, g.gstate[:R], off, data, table, eos, g.valid[:R])
+        if g.greedy:
+            if g.penalized:
+                nxt = self._penalized_greedy(logits, g, full=full)
+            else:
+                nxt = ops.argmax(full)
+        else:
+            src = full
+            if g.penalized:
+                src = full.float().clone(memory_format=torch.contiguous_format)
+                ops.apply_penalties(src, g.hist[:R], g.hist_n[:R], g.last_n[:R], g.rep_pen[:R], g.pres_pen[:R],
+                                    g.freq_pen[:R], g.valid[:R])
+            if g.seeded:
+                nxt = ops.sample_tokens(src, V, g.inv_temp, g.top_k, g.top_p, g.min_p,
+                                        seed=g.seed, index=g.context_lens, valid=g.valid)
+            else:
+                nxt = ops.sample_tokens(src, V, g.inv_temp, g.top_k, g.top_p, g.min_p,
+                                        u=torch.rand(R, device=src.device))
+        nxt = nxt.long().contiguous()
+        if raw is not None:
+            ops.token_logprobs(raw, V, nxt, g.lp_n[:R], g.lp[:R], g.lp_top_ids[:R], g.lp_top[:R])
+        ops.grammar_advance(g.gstate[:R], nxt, off, data, table, eos, g.valid[:R])
+        return nxt
+
     def _get_graph(self, bp: int, greedy: bool, cascade: bool = False, fit: bool = True,
-                   penalized: bool = False, logprobs: bool = False, min_p: bool = False) -> _DecodeGraph:
+                   penalized: bool = False, logprobs: bool = False, min_p: bool = False,
+                   constrained: bool = False) -> _DecodeGraph:
         """``min_p``: the sampled flavour whose pick is ops.sample_tokens -- graphs of their own
-        under the same key, so the key and the graphs without min_p stay what they were."""
+        under the same key, so the key and the graphs without min_p stay what they were.
+        ``constrained``: the grammar flavours, kept apart the same way."""
         fit = fit or self.max_blocks_per_seq <= ops.GROUP_MAX_BLOCKS
         key = (bp, greedy, cascade, fit, penalized, logprobs)
-        graphs = self._graphs_min_p if min_p else self._graphs
+        graphs = self._graphs_json if constrained else self._graphs_min_p if min_p else self._graphs
         g = graphs.get(key)
         if g is None:
             g = _DecodeGraph(self, bp)
+            g.constrained = constrained
             g.min_p_on = min_p
             g.greedy = greedy
             g.penalized = penalized
@@ -827,7 +919,8 @@ class LLMEngine:
             if rot > 0 and hasattr(tunable, "set_rotating_buffer_size"):
                 tunable.set_rotating_buffer_size(rot)
         # the eager warm-up step advances the slot state (and the penalised flavours' rings)
-        state = (g.tokens, g.positions, g.context_lens) + ((g.hist, g.hist_n) if g.penalized else ())
+        state = ((g.tokens, g.positions, g.context_lens) + ((g.hist, g.hist_n) if g.penalized else ())
+                 + ((g.gstate,) if g.constrained else ()))
         saved = [t.clone() for t in state]
         try:
             s = torch.cuda.Stream()
@@ -1008,6 +1101,7 @@ class LLMEngine:
         B = len(prompts)
         if B > self.max_batch:
             raise ValueError(f"launch: {B} prompts > max_batch {self.max_batch}")
+        self.require_grammar(params)
         dev = self.device
         cuda = dev.type == "cuda"
         lens = [len(p) for p in prompts]
@@ -1022,6 +1116,7 @@ class LLMEngine:
             greedy = params.temperature <= 0.0
             penalized = not params.neutral
             want_lp = params.logprobs
+            constrained = params.constrained
             t0 = time.perf_counter()
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if cuda else None
             if cuda:
@@ -1030,7 +1125,8 @@ class LLMEngine:
             with tracing.span("engine.prefill", seqs=B, tokens=sum(lens) - sum(cached)):
                 # penalised requests pick their first token under the penalties too: logits;
                 # so do requests with logprobs, whose first token is covered like every other
-                logits = self._prefill(prompts, tables, cached, greedy=greedy and not penalized and not want_lp)
+                # and constrained ones, whose first token is masked from the start state
+                logits = self._prefill(prompts, tables, cached, greedy=params.fused_greedy_ok)
             if use_pc:
                 with tracing.span("engine.register", seqs=B):
                     self.register_prefixes(prompts, tables, r.keys)
@@ -1041,7 +1137,7 @@ class LLMEngine:
             fit = self.groups_fit([n + params.max_new_tokens for n in lens])
             grouped = nshared > 0 or self.group_without_prefix(B, fit)
             g = self._get_graph(_bucket(B, self.max_batch) if self.use_graphs else B, greedy, grouped, fit,
-                                penalized, want_lp, min_p=not greedy and params.min_p > 0)
+                                penalized, want_lp, min_p=not greedy and params.min_p > 0, constrained=constrained)
             if grouped:
                 g.shared_len.fill_(0)
             if nshared:
@@ -1073,6 +1169,13 @@ class LLMEngine:
                 g.min_p.fill_(params.min_p)
                 if params.seed:
                     torch.manual_seed(params.seed)
+            if constrained:
+                # every row of the batch starts the object; the bucket's padding slots stay out
+                from ..ops import grammar
+
+                gs = torch.zeros(g.bp, dtype=torch.int64)
+                gs[:B] = grammar.START_STATE
+                _upload(g.gstate, gs)
             if want_lp:
                 # every row of the batch asks for the same; the bucket's padding slots for nothing
                 ln = torch.full((g.bp,), -1, dtype=torch.int32)
@@ -1091,13 +1194,17 @@ class LLMEngine:
                 g.rep_pen.fill_(params.repeat_penalty)
                 g.pres_pen.fill_(params.presence_penalty)
                 g.freq_pen.fill_(params.frequency_penalty)
-                if want_lp:
+                if constrained:
+                    first = self._pick_constrained(logits, g)
+                elif want_lp:
                     first = self._pick_logprobs(logits, g)
                 else:
                     first = self._penalized_greedy(logits, g) if greedy else self._select(logits, g)
                 rows = torch.arange(B, device=dev)
                 g.hist[rows, (g.hist_n[:B] % W).long()] = first.int()
                 g.hist_n[:B] += 1
+            elif constrained:
+                first = self._pick_constrained(logits, g)
             elif want_lp:
                 first = self._pick_logprobs(logits, g)
             else:

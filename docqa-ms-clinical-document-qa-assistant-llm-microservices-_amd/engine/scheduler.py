@@ -200,6 +200,12 @@ class ContinuousEngine:
         token; a true result finishes the request there (stop strings -- the caller owns the
         tokenizer).  A check that raises is dropped, like ``on_token``."""
         params = params or SamplingParams()
+        if params.constrained:
+            # the grammar state lives in the slot state of the decode graphs: a mixed step's
+            # eager forward does not carry it
+            if self.mixed:
+                raise ValueError('format "json" is not served with mixed steps (DOCQA_MIXED_PREFILL=1)')
+            self.eng.require_grammar(params)
         fut: cf.Future = cf.Future()
         if len(prompt) + params.max_new_tokens > self.eng.max_context or not prompt:
             fut.set_exception(ValueError(
@@ -708,6 +714,10 @@ class ContinuousEngine:
         ln = torch.zeros(k, dtype=torch.int32)
         pen = torch.tensor([[1.0, 0.0, 0.0]] * k, dtype=torch.float32)
         lpn = torch.tensor([r.params.lp_n for r in reqs], dtype=torch.int32)   # -1: did not ask
+        # grammar: the automaton after the request's output so far -- the first token, and after a
+        # preemption every token already folded into the resumed prompt; 0: not constrained
+        gst = torch.tensor([self.eng.grammar_state(r.out) if r.params.constrained else 0 for r in reqs],
+                           dtype=torch.int64)
         for i, r in enumerate(reqs):
             if not r.params.neutral:
                 hist[i], hn[i] = ring_of(self._stream(r), W)
@@ -744,6 +754,7 @@ class ContinuousEngine:
         m.pres_pen[sl].copy_(pen[:, 1].contiguous().to(dev, non_blocking=True))
         m.freq_pen[sl].copy_(pen[:, 2].contiguous().to(dev, non_blocking=True))
         m.lp_n[sl].copy_(lpn.to(dev, non_blocking=True))
+        m.gstate[sl].copy_(gst.to(dev, non_blocking=True))
         self.running.extend(reqs)
         self._version += 1
 
@@ -779,11 +790,23 @@ class ContinuousEngine:
         resumed request's prompt already holds its earlier output), from the request's seed."""
         model = self.eng.model
         params = [r.params for r in reqs]
-        if all(p.temperature <= 0.0 and p.neutral for p in params):
+        constrained = any(p.constrained for p in params)
+        if all(p.temperature <= 0.0 and p.neutral for p in params) and not constrained:
             # greedy neutral rows (with logprobs: the argmax of the logits they come from)
             return model.greedy(logits).tolist()
         full = model.full_logits(logits)
         dev = full.device
+        if constrained:
+            # the first token is masked too, from the state of the output so far (the start state
+            # unless the request was preempted); unconstrained rows carry state 0
+            if keep:
+                full = full.clone()
+            off, data, table = self.eng._grammar
+            gst = torch.tensor([self.eng.grammar_state(r.out) if r.params.constrained else 0 for r in reqs],
+                               dtype=torch.int64, device=dev)
+            ops.grammar_mask(full, self.eng.cfg.vocab_size, gst, off, data, table, self.eng.cfg.eos_token_id)
+            if all(p.temperature <= 0.0 and p.neutral for p in params):
+                return ops.argmax(full).tolist()
         pen = None
         if not all(p.neutral for p in params):
             W = ops.PENALTY_WINDOW
@@ -809,13 +832,16 @@ class ContinuousEngine:
         return ops.sample_tokens(full, self.eng.cfg.vocab_size, it, tk, tp, mp, seed=seed, index=index).tolist()
 
     def _graph(self, bp: int, greedy: bool, cascade: bool, fit: bool = True,
-               penalized: bool = False, logprobs: bool = False) -> _DecodeGraph:
+               penalized: bool = False, logprobs: bool = False, constrained: bool = False) -> _DecodeGraph:
+        """``constrained``: the grammar flavours, under keys one entry longer -- the other
+        flavours' keys and graphs stay what they were."""
         fit = fit or self._master.groups_fit
-        key = (bp, greedy, cascade, fit, penalized, logprobs)
+        key = (bp, greedy, cascade, fit, penalized, logprobs) + (("json",) if constrained else ())
         g = self._graphs.get(key)
         if g is None:
             g = _DecodeGraph.view_of(self._master, bp)
             g.greedy, g.cascade, g.groups_fit = greedy, cascade, fit
+            g.constrained = constrained
             g.penalized = penalized
             g.logprobs = logprobs
             g.seeded = True      # this scheduler's graphs sample per slot from (seed, position)
@@ -913,7 +939,9 @@ class ContinuousEngine:
         grouped = self._nshared > 0 or eng.group_without_prefix(n, fit)
         # any running row asks for logprobs: the flavour that computes them (for those rows only)
         want_lp = any(r.params.logprobs for r in self.running)
-        g = self._graph(bp, greedy, grouped, fit, penalized, want_lp)
+        # any running row is grammar-constrained: the flavour that masks and advances (those rows only)
+        constrained = any(r.params.constrained for r in self.running)
+        g = self._graph(bp, greedy, grouped, fit, penalized, want_lp, constrained)
         if eng.lpt:
             # re-rank only when the running set changed (admission / retirement)
             eng.set_order(g, [len(r.prompt) + len(r.out) for r in self.running], key=self._version)
@@ -1045,10 +1073,12 @@ class ContinuousEngine:
         if keep != list(range(k)):
             idx = torch.tensor(keep, dtype=torch.long, device=m.tokens.device)
             for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
-                         "top_k", "top_p", "min_p", "seed", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen", "lp_n"):
+                         "top_k", "top_p", "min_p", "seed", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen", "lp_n",
+                         "gstate"):
                 t = getattr(m, name)
                 t[:k] = t[idx]
         m.lp_n[k:n].fill_(-1)
+        m.gstate[k:n].zero_()
         m.valid[k:n].zero_()
         m.context_lens[k:n].zero_()
         m.positions[k:n].zero_()

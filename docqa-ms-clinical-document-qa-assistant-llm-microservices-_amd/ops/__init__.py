@@ -1482,6 +1482,33 @@ def token_logprobs(logits, n_valid: int, chosen, top_n, lp=None, top_ids=None, t
     return lp, top_ids, top_lp
 
 
+def grammar_mask(logits, n_valid: int, state, tok_off, tok_bytes, table, eos_id: int, valid=None) -> None:
+    """Grammar-constrained decoding (:mod:`docqa_amd.ops.grammar`, csrc/kernels/grammar.hip): in
+    place on bf16 / fp32 logits [R, ld], every row with ``state != 0`` (int64 [R], the row's
+    automaton state) and ``valid != 0`` gets ``-inf`` in each column ``t < n_valid`` whose token is
+    not allowed: allowed is a token with bytes (``tok_off`` int32 [V + 1] into ``tok_bytes``
+    uint8) that walk from the state through ``table`` (int16 [states, 256]) without a reject, or
+    ``t == eos_id`` in DONE -- EOS is never allowed before DONE, a token without bytes or past
+    the byte table never.  Allowed columns, columns at or past ``n_valid`` and skipped rows are
+    left bit for bit; no logit is read."""
+    if _gpu(logits):
+        _native().grammar_mask(logits, int(n_valid), state, tok_off, tok_bytes, table, int(eos_id), valid)
+        return
+    ref.grammar_mask(logits, int(n_valid), state, tok_off, tok_bytes, table, int(eos_id), valid)
+
+
+def grammar_advance(state, nxt, tok_off, tok_bytes, table, eos_id: int, valid=None) -> None:
+    """In place on ``state`` int64 [R]: the automaton after the bytes of the picked token
+    ``nxt`` (int64 [R]).  State 0 stays 0, DONE stays DONE (the extra lagged step of a finished
+    request picks EOS again), EOS leaves the state as it is, and so does a token that would be
+    rejected (defensive: it cannot occur behind :func:`grammar_mask`).  GPU and CPU agree as
+    int64."""
+    if _gpu(state):
+        _native().grammar_advance(state, nxt, tok_off, tok_bytes, table, int(eos_id), valid)
+        return
+    ref.grammar_advance(state, nxt, tok_off, tok_bytes, table, int(eos_id), valid)
+
+
 def decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n) -> None:
     """:func:`decode_advance`, and the valid rows' new token joins their ring:
     hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1."""

@@ -617,3 +617,90 @@ def coarse_probes(xq, centroids, cnorm, nprobe: int):
     d = cnorm.float()[None, :] - 2.0 * (xq.float() @ centroids.float().t())
     order = torch.sort(d, dim=1, stable=True).indices
     return order[:, :nprobe].contiguous()
+
+
+# ----------------------------------------------------------------------------- grammar (format: "json")
+def _grammar_allowed(state: int, n: int, off, data, tab, eos_id: int):
+    """bool [n]: which of the tokens [0, n) a row in ``state`` (non-zero) may emit -- every token
+    walked at once, one byte position per numpy pass over the tokens still alive."""
+    import numpy as np
+
+    from . import grammar as G
+
+    allowed = np.zeros(n, dtype=bool)
+    if G.is_done(state):
+        if 0 <= eos_id < n:
+            allowed[eos_id] = True
+        return allowed
+    nt = min(n, len(off) - 1)
+    lens = (off[1:nt + 1] - off[:nt]).astype(np.int64)
+    idx = np.nonzero(lens > 0)[0]
+    lex0, ws0, depth0, stack0 = G.unpack(state)
+    lex = np.full(idx.size, lex0, dtype=np.int64)
+    ws = np.full(idx.size, ws0, dtype=np.int64)
+    depth = np.full(idx.size, depth0, dtype=np.int64)
+    stack = np.full(idx.size, stack0, dtype=np.int64)
+    j = 0
+    while idx.size:
+        ok = lex < tab.shape[0]
+        e = tab[np.minimum(lex, tab.shape[0] - 1), data[off[idx] + j]].astype(np.int64)
+        nxt, op = e & 0xFF, e >> 8
+        top = stack >> np.maximum(depth - 1, 0) & 1
+        is_ws, push, pop = op == G.OP_WS, (op == G.OP_PUSH_OBJ) | (op == G.OP_PUSH_ARR), \
+            (op == G.OP_POP_OBJ) | (op == G.OP_POP_ARR)
+        ok &= op != G.OP_REJECT
+        ok &= ~(is_ws & (ws >= G.WS_CAP))
+        ok &= ~(push & (depth >= G.DEPTH_CAP))
+        ok &= ~(pop & ((depth == 0) | (top != (op == G.OP_POP_ARR))))
+        ok &= ~((op == G.OP_COMMA) & (depth == 0))
+        ws = np.where(is_ws, ws + 1, 0)
+        stack = np.where(push, stack | (op == G.OP_PUSH_ARR).astype(np.int64) << np.minimum(depth, 62), stack)
+        depth = depth + push - pop
+        stack = np.where(pop, stack & ~(np.int64(1) << np.maximum(depth, 0)), stack)
+        lex = np.where(pop, np.where(depth == 0, G.DONE, G.AFTER_VALUE),
+                       np.where(op == G.OP_COMMA, np.where(top == 1, G.EXPECT_VALUE, G.EXPECT_KEY), nxt))
+        j += 1
+        ended = ok & (lens[idx] == j)
+        allowed[idx[ended]] = True
+        go = ok & ~ended
+        idx, lex, ws, depth, stack = idx[go], lex[go], ws[go], depth[go], stack[go]
+    if 0 <= eos_id < n:
+        allowed[eos_id] = False      # EOS only in DONE, whatever bytes it has
+    return allowed
+
+
+def grammar_mask(logits, n_valid: int, state, tok_off, tok_bytes, table, eos_id: int, valid=None) -> None:
+    """In place: -inf into every column t < n_valid of a constrained row (state != 0, valid != 0)
+    whose token the row's automaton state does not allow (ops.grammar); nothing else is written.
+    Rows in the same state share one walk of the vocabulary."""
+    off, data, tab = tok_off.cpu().numpy(), tok_bytes.cpu().numpy(), table.cpu().numpy()
+    states = state.tolist()
+    cache: dict = {}
+    for r in range(logits.shape[0]):
+        s = states[r]
+        if s == 0 or (valid is not None and int(valid[r]) == 0):
+            continue
+        if s not in cache:
+            cache[s] = torch.from_numpy(~_grammar_allowed(s, int(n_valid), off, data, tab, int(eos_id)))
+        logits[r, :n_valid].masked_fill_(cache[s].to(logits.device), -math.inf)
+
+
+def grammar_advance(state, nxt, tok_off, tok_bytes, table, eos_id: int, valid=None) -> None:
+    """In place on state int64 [R]: the automaton after the bytes of token nxt[i]; 0 and DONE
+    stay, EOS and a token that would be rejected leave the state unchanged."""
+    from . import grammar as G
+
+    off, data = tok_off.cpu().numpy(), tok_bytes.cpu().numpy()
+    tab = table.cpu().numpy().astype("int32").tolist()
+    states, toks = state.tolist(), nxt.tolist()
+    for r, (s, t) in enumerate(zip(states, toks)):
+        if s == 0 or G.is_done(s) or t == eos_id or (valid is not None and int(valid[r]) == 0):
+            continue
+        if not 0 <= t < len(off) - 1 or off[t + 1] == off[t]:
+            continue
+        for b in data[off[t]:off[t + 1]].tolist():
+            s = G.step(s, b, tab)
+            if s < 0:
+                break
+        if s >= 0:
+            state[r] = s

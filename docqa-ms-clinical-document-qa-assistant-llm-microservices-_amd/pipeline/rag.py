@@ -78,6 +78,14 @@ class RAGPipeline:
         self.metadata = metadata
         self.engine = engine
         self.chat_tok = chat_tokenizer
+        # format: "json" -- the engine masks tokens by their bytes (LLMEngine.set_vocab_bytes); a
+        # tokenizer without all 256 single-byte tokens leaves it unset and such requests refused
+        if (hasattr(engine, "set_vocab_bytes") and engine.vocab_bytes is None
+                and hasattr(chat_tokenizer, "token_bytes")):
+            try:
+                engine.set_vocab_bytes(chat_tokenizer.token_bytes(engine.cfg.vocab_size))
+            except ValueError:
+                pass
         self.k = k
         self.template = template
         self.max_prompt_tokens = max_prompt_tokens

@@ -161,6 +161,12 @@ def run_parallel(a, opts: "StackOptions") -> None:
         ctx = min(opts.max_context or st.max_context, model.cfg.max_position)
         eng = LLMEngine(model, max_batch=opts.max_batch, max_context=ctx, use_graphs=opts.use_graphs,
                         kv_mem_fraction=opts.kv_mem_fraction)
+        try:   # the leader's pipeline does the same: constrained requests mask by token bytes
+            from ..text.tokenizer import ChatTokenizer
+
+            eng.set_vocab_bytes(ChatTokenizer(model_vocab=model.cfg.vocab_size).token_bytes(model.cfg.vocab_size))
+        except ValueError:
+            pass
         ce = ContinuousEngine(eng, max_running=st.max_batch, lockstep=ls)
         if os.environ.get("DOCQA_WARM_BUCKETS", "1") == "1":
             from ..engine.llm_engine import SamplingParams

@@ -12,7 +12,8 @@ other request in flight) instead of a llama.cpp process.
                        "options": {"temperature", "num_predict", "top_k", "top_p", "min_p",
                                    "seed", "repeat_penalty", "repeat_last_n", "presence_penalty",
                                    "frequency_penalty", "stop"},
-                       "logprobs" (default false), "top_logprobs" (0..20)}
+                       "logprobs" (default false), "top_logprobs" (0..20),
+                       "format": "json" | a JSON-schema object (absent / null / "": off)}
                       -> {"model", "created_at", "message": {"role": "assistant", "content"},
                           "done": true, "done_reason": "stop" | "length", "total_duration",
                           "load_duration", "prompt_eval_count", "prompt_eval_duration",
@@ -39,7 +40,16 @@ Deviations, by design: one model per process (the request's "model" is echoed, n
 pick weights); "temperature" defaults to the service's TEMPERATURE (0, the reference's
 setting) rather than Ollama's 0.8, and the penalties to the service's neutral REPEAT_PENALTY /
 REPEAT_LAST_N / PRESENCE_PENALTY / FREQUENCY_PENALTY rather than Ollama's 1.1 over 64 tokens
-(docs/CONFIG.md); "format", "keep_alive", "images" and "tools" are ignored.  "stop" (a string
+(docs/CONFIG.md); "keep_alive", "images" and "tools" are ignored.  "format": "json" constrains
+the completion to ONE JSON object on the device (ops/grammar.py, csrc/kernels/grammar.hip: every
+step masks the tokens that would leave llama.cpp's json.gbnf with an object root, EOS is allowed
+only once the object has closed), so whenever done_reason is "stop" by EOS the text parses with
+json.loads; "length" means num_predict cut the object short, as with Ollama.  Two caps keep a
+model from looping: a run of more than 16 whitespace characters outside strings and nesting deeper
+than 32 are not generated.  A JSON-schema OBJECT as "format" is accepted and constrains to a JSON
+object, but the schema itself is NOT enforced yet (Ollama compiles it to a grammar; here that is
+a different transition table, left as the follow-up).  Any other "format" is a 400 {"error"}.
+"logprobs" stay the model's own distribution, from the logits before the grammar mask.  "stop" (a string
 or a list) ends the text just before the earliest match with done_reason "stop"; a streamed
 tail that could still grow into a stop string is held back until it is resolved.
 Temperature comes FIRST: top_k, top_p and min_p filter the distribution at the request's
@@ -84,6 +94,7 @@ class OllamaChatRequest(BaseModel):
     options: dict | None = None
     logprobs: bool = False
     top_logprobs: int = 0
+    format: object = None
 
 
 class OllamaGenerateRequest(BaseModel):
@@ -95,6 +106,18 @@ class OllamaGenerateRequest(BaseModel):
     options: dict | None = None
     logprobs: bool = False
     top_logprobs: int = 0
+    format: object = None
+
+
+def format_from_request(fmt) -> str:
+    """The request's ``format`` as ``SamplingParams.format``: absent / null / "" is off, "json"
+    and a JSON-schema object constrain to a JSON object (the schema is not enforced yet).  Raises
+    ValueError (the routes answer 400) on anything else."""
+    if fmt is None or fmt == "":
+        return ""
+    if fmt == "json" or isinstance(fmt, dict):
+        return "json"
+    raise ValueError('format must be "json" or a JSON schema object')
 
 
 def _now() -> str:
@@ -197,7 +220,7 @@ def register(app: FastAPI, settings, metrics) -> None:
         return ids if not lim or len(ids) <= lim else ids[: lim // 2] + ids[-(lim // 2):]
 
     async def _run(kind: str, model: str, ids: list[int], options: dict | None, stream: bool,
-                   logprobs: bool = False, top_logprobs: int = 0):
+                   logprobs: bool = False, top_logprobs: int = 0, fmt=None):
         pipe, batcher = app.state.pipeline, app.state.batcher
         if pipe is None or batcher is None:
             return JSONResponse(status_code=503, content={"error": "model not loaded"})
@@ -208,6 +231,11 @@ def register(app: FastAPI, settings, metrics) -> None:
         ids = _prompt_ids(pipe, ids)
         try:
             params = sampling_from_options(options, settings, pipe.engine.max_context, len(ids))
+            params.format = format_from_request(fmt)
+            if params.constrained:
+                if getattr(getattr(batcher, "engine", None), "mixed", False):
+                    raise ValueError('format "json" is not served with mixed steps (DOCQA_MIXED_PREFILL=1)')
+                pipe.engine.require_grammar(params)
         except ValueError as e:
             return JSONResponse(status_code=400, content={"error": str(e)})
         params.logprobs, params.top_logprobs = bool(logprobs), int(top_logprobs)
@@ -320,7 +348,8 @@ def register(app: FastAPI, settings, metrics) -> None:
         if pipe is None:
             return JSONResponse(status_code=503, content={"error": "model not loaded"})
         ids = pipe.chat_tok.chat_messages([m.model_dump() for m in req.messages])
-        return await _run("chat", req.model, ids, req.options, req.stream, req.logprobs, req.top_logprobs)
+        return await _run("chat", req.model, ids, req.options, req.stream, req.logprobs, req.top_logprobs,
+                          req.format)
 
     @app.post("/api/generate")
     async def ollama_generate(req: OllamaGenerateRequest):
@@ -332,7 +361,8 @@ def register(app: FastAPI, settings, metrics) -> None:
             ids = tok.encode(req.prompt)
         else:
             ids = tok.chat_prompt(req.prompt, system=req.system)
-        return await _run("generate", req.model, ids, req.options, req.stream, req.logprobs, req.top_logprobs)
+        return await _run("generate", req.model, ids, req.options, req.stream, req.logprobs, req.top_logprobs,
+                          req.format)
 
     @app.get("/api/tags")
     def ollama_tags():

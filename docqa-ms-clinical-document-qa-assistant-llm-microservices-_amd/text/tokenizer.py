@@ -111,6 +111,19 @@ class WordPieceTokenizer:
         return out
 
 
+def _bytes_to_unicode() -> dict[int, str]:
+    """The ByteLevel pre-tokenizer's alphabet: byte -> the printable character that stands for
+    it in token strings (GPT-2's map: printable Latin-1 bytes are themselves, the other 68
+    bytes take the code points from 256 up, in byte order)."""
+    keep = list(range(0x21, 0x7F)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+    out, n = {b: chr(b) for b in keep}, 0
+    for b in range(256):
+        if b not in out:
+            out[b] = chr(256 + n)
+            n += 1
+    return out
+
+
 class ChatTokenizer:
     """Byte-level BPE with Llama-3 chat framing.  Special tokens are remapped onto the
     Llama-3 special-id range (128000+) so the model config keeps Llama-3's ids."""
@@ -182,6 +195,32 @@ class ChatTokenizer:
             if 0 <= i < self.n:
                 keep.append(i)
         return self.tok.decode(keep)
+
+    def token_bytes(self, model_vocab: int | None = None) -> list[bytes]:
+        """The raw bytes of every model token id in [0, model_vocab): the ByteLevel alphabet (the
+        GPT-2 byte <-> unicode map) inverted.  ``b""`` for special tokens and for ids the
+        tokenizer does not have (a random-init model's ids past its vocabulary).  Raises
+        ValueError when one of the 256 single-byte strings has no token: grammar-constrained
+        decoding relies on them (ops.grammar.vocab_tensors)."""
+        n_model = self.model_vocab if model_vocab is None else model_vocab
+        u2b = {u: b for b, u in _bytes_to_unicode().items()}
+        special = {tid for tid, t in self.tok.get_added_tokens_decoder().items() if t.special}
+        special |= set(self._to_model)
+        out = [b""] * n_model
+        for mid in range(min(n_model, self.n)):
+            if mid in self._from_model or mid in special:
+                continue
+            s = self.tok.id_to_token(mid)
+            if s is None:
+                continue
+            try:
+                out[mid] = bytes(u2b[c] for c in s)
+            except KeyError:          # an added token outside the byte alphabet: its text
+                out[mid] = s.encode("utf-8")
+        have = {b for b in out if len(b) == 1}
+        if len(have) < 256:
+            raise ValueError(f"tokenizer has single-byte tokens for {len(have)} of the 256 bytes")
+        return out
 
     def encode_batch_chat(self, users: list[str]) -> list[list[int]]:
         """chat_prompt for many user turns: the user texts are tokenised in one
