@@ -670,6 +670,71 @@ void grammar_advance(at::Tensor state, const at::Tensor& nxt, const at::Tensor& 
                                  stream()), "grammar_advance");
 }
 
+// JSON-schema structured outputs: the shared checks of the vocabulary-bytes table and the pool
+static void check_schema(const char* op, const at::Tensor& ref, int64_t R, const at::Tensor& sstate,
+                         const at::Tensor& tok_off, const at::Tensor& tok_bytes, const at::Tensor& pool,
+                         const c10::optional<at::Tensor>& valid) {
+  const auto on_dev = [&](const at::Tensor& t) { return t.is_cuda() && t.device() == ref.device(); };
+  TORCH_CHECK(on_dev(sstate) && on_dev(tok_off) && on_dev(tok_bytes) && on_dev(pool), op,
+              ": every tensor on one device");
+  TORCH_CHECK(sstate.scalar_type() == at::kLong && sstate.is_contiguous() && sstate.numel() == R, op,
+              ": sstate must be contiguous int64 [rows]");
+  TORCH_CHECK(tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.numel() >= 1, op,
+              ": tok_off must be contiguous int32 [V + 1]");
+  TORCH_CHECK(tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
+                  tok_bytes.numel() < (int64_t(1) << 31), op, ": tok_bytes must be contiguous uint8");
+  TORCH_CHECK(pool.scalar_type() == at::kByte && pool.is_contiguous() && pool.dim() == 2 &&
+                  pool.size(1) == docqa_schema_slot_bytes() && pool.size(0) >= 1 && pool.size(0) <= 256,
+              op, ": pool must be contiguous uint8 [1..256 slots, ", docqa_schema_slot_bytes(), "]");
+  CHECK_ALIGN16(pool);
+  if (valid.has_value() && valid->defined())
+    TORCH_CHECK(on_dev(*valid) && valid->scalar_type() == at::kInt && valid->is_contiguous() &&
+                    valid->numel() >= R, op, ": valid must be contiguous int32 [>= rows]");
+}
+
+// in place: -inf into every column t < n_valid of a schema row (word != 0, valid != 0) whose token
+// the automaton of the row's pool slot does not allow; nothing else is written
+void schema_mask(at::Tensor logits, int64_t n_valid, const at::Tensor& sstate, const at::Tensor& tok_off,
+                 const at::Tensor& tok_bytes, const at::Tensor& pool, int64_t eos_id,
+                 const c10::optional<at::Tensor>& valid) {
+  CHECK_GPU(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "schema_mask wants [rows, V] with unit stride");
+  const bool bf = logits.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || logits.scalar_type() == at::kFloat, "schema_mask: bf16 or fp32 logits");
+  const int64_t R = logits.size(0), V = logits.size(1), ld = logits.stride(0);
+  TORCH_CHECK(n_valid >= 1 && n_valid <= V, "schema_mask: n_valid must be in [1, V]");
+  TORCH_CHECK(R <= 1 || ld >= V, "schema_mask: row stride below V");
+  TORCH_CHECK(R <= 65535, "schema_mask: at most 65535 rows");
+  check_schema("schema_mask", logits, R, sstate, tok_off, tok_bytes, pool, valid);
+  if (R == 0) return;
+  c10::DeviceGuard g(logits.device());
+  CHECK_RC(docqa_schema_mask(logits.data_ptr(), (int)R, (int)n_valid, (long)ld, bf ? 1 : 0,
+                             sstate.data_ptr<int64_t>(), valid_ptr(valid), tok_off.data_ptr<int>(),
+                             (int)tok_off.numel() - 1, tok_bytes.numel() ? tok_bytes.data_ptr<uint8_t>() : nullptr,
+                             (int)tok_bytes.numel(), pool.data_ptr<uint8_t>(), (int)pool.size(0), (int)eos_id,
+                             stream()),
+           "schema_mask");
+}
+
+// in place: sstate[i] <- the word after the bytes of token nxt[i] (0, DONE, EOS and a token that
+// would be rejected leave it as it is)
+void schema_advance(at::Tensor sstate, const at::Tensor& nxt, const at::Tensor& tok_off,
+                    const at::Tensor& tok_bytes, const at::Tensor& pool, int64_t eos_id,
+                    const c10::optional<at::Tensor>& valid) {
+  CHECK_GPU(sstate);
+  const int64_t R = sstate.numel();
+  TORCH_CHECK(nxt.is_cuda() && nxt.device() == sstate.device() && nxt.scalar_type() == at::kLong &&
+                  nxt.is_contiguous() && nxt.numel() == R, "schema_advance: nxt must be contiguous int64 [rows]");
+  check_schema("schema_advance", sstate, R, sstate, tok_off, tok_bytes, pool, valid);
+  if (R == 0) return;
+  c10::DeviceGuard g(sstate.device());
+  CHECK_RC(docqa_schema_advance(sstate.data_ptr<int64_t>(), nxt.data_ptr<int64_t>(), (int)R, valid_ptr(valid),
+                                tok_off.data_ptr<int>(), (int)tok_off.numel() - 1,
+                                tok_bytes.numel() ? tok_bytes.data_ptr<uint8_t>() : nullptr,
+                                (int)tok_bytes.numel(), pool.data_ptr<uint8_t>(), (int)pool.size(0), (int)eos_id,
+                                stream()), "schema_advance");
+}
+
 // decode_advance + the ring: hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1 for valid rows
 void decode_advance_hist(const at::Tensor& nxt, at::Tensor out, at::Tensor tokens, at::Tensor positions,
                          at::Tensor context_lens, const at::Tensor& valid, at::Tensor hist,
@@ -1992,6 +2057,10 @@ TORCH_LIBRARY(docqa, m) {
         "Tensor table, int eos_id, Tensor? valid=None) -> ()");
   m.def("grammar_advance(Tensor(a!) state, Tensor nxt, Tensor tok_off, Tensor tok_bytes, Tensor table, "
         "int eos_id, Tensor? valid=None) -> ()");
+  m.def("schema_mask(Tensor(a!) logits, int n_valid, Tensor sstate, Tensor tok_off, Tensor tok_bytes, "
+        "Tensor pool, int eos_id, Tensor? valid=None) -> ()");
+  m.def("schema_advance(Tensor(a!) sstate, Tensor nxt, Tensor tok_off, Tensor tok_bytes, Tensor pool, "
+        "int eos_id, Tensor? valid=None) -> ()");
   m.def("top_logprobs_max() -> int", &top_logprobs_max);
   m.def("token_logprobs(Tensor logits, int n_valid, Tensor chosen, Tensor top_n, Tensor(a!) lp, "
         "Tensor(b!) top_ids, Tensor(c!) top_lp) -> ()");
@@ -2114,6 +2183,8 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("penalized_argmax", &penalized_argmax);
   m.impl("grammar_mask", &grammar_mask);
   m.impl("grammar_advance", &grammar_advance);
+  m.impl("schema_mask", &schema_mask);
+  m.impl("schema_advance", &schema_advance);
   m.impl("token_logprobs", &token_logprobs);
   m.impl("decode_advance_hist", &decode_advance_hist);
   m.impl("paged_decode", &paged_decode);

@@ -112,6 +112,18 @@ int docqa_grammar_advance(int64_t* state, const int64_t* nxt, int rows, const in
                           int n_tok, const uint8_t* tok_bytes, int total, const void* table, int n_states,
                           int eos_id, hipStream_t s);
 
+// JSON-schema structured outputs (grammar_schema.hip): per-row state words (0: no schema; DFA
+// state, whitespace run, pool slot) and the table pool uint8 [n_slots, docqa_schema_slot_bytes()],
+// one compiled automaton (ops/json_schema.py) per slot.  mask / advance: the contracts of the
+// grammar pair, each row walking the tables of its own slot.
+long docqa_schema_slot_bytes();
+int docqa_schema_mask(void* logits, int rows, int n_valid, long ld, int is_bf16, const int64_t* sstate,
+                      const int* valid, const int* tok_off, int n_tok, const uint8_t* tok_bytes, int total,
+                      const uint8_t* pool, int n_slots, int eos_id, hipStream_t s);
+int docqa_schema_advance(int64_t* sstate, const int64_t* nxt, int rows, const int* valid, const int* tok_off,
+                         int n_tok, const uint8_t* tok_bytes, int total, const uint8_t* pool, int n_slots,
+                         int eos_id, hipStream_t s);
+
 int docqa_paged_decode(const void* q, int q_stride, const void* k_cache, const void* v_cache,
                        const int* block_tables, int maxb, const int* context_lens, void* out,
                        int out_stride, float* tmp_out, float* tmp_ml, int B, int Hq, int Hkv,

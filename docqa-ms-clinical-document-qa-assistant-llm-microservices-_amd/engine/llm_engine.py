@@ -73,11 +73,41 @@ class SamplingParams:
     # (ops.grammar: whitespace runs <= 16, nesting <= 32), EOS allowed only once it has closed;
     # "" is off.  Needs the vocabulary's bytes on the engine (LLMEngine.set_vocab_bytes).
     format: str = ""
+    # a JSON-schema object (needs format "json"): the output is a prefix of one document of the
+    # schema's language (ops.json_schema: the supported subset, properties in declared order);
+    # compiled here, so an unsupported schema raises ValueError before the request is admitted
+    json_schema: dict | None = None
 
     def __post_init__(self):
         self.top_logprobs = max(0, min(int(self.top_logprobs), ops.TOP_LOGPROBS_MAX))
         if self.format not in ("", "json"):
             raise ValueError(f'format must be "" or "json", got {self.format!r}')
+        self.set_json_schema(self.json_schema)
+
+    def set_json_schema(self, schema: dict | None) -> None:
+        """Set (and compile) ``json_schema``; ValueError names the keyword that is not supported."""
+        self._compiled = None
+        if schema is not None:
+            if self.format != "json":
+                raise ValueError('json_schema needs format "json"')
+            from ..ops import json_schema
+
+            self._compiled = json_schema.compile_schema(schema)
+        self.json_schema = schema
+
+    @property
+    def schema_constrained(self) -> bool:
+        """The request's tokens are masked by its schema's automaton (and not by the JSON one)."""
+        return self.json_schema is not None
+
+    @property
+    def compiled_schema(self):
+        """ops.json_schema.CompiledSchema of ``json_schema``, or None."""
+        return self._compiled
+
+    @property
+    def schema_key(self) -> str:
+        return self._compiled.key if self._compiled is not None else ""
 
     @property
     def constrained(self) -> bool:
@@ -100,6 +130,47 @@ class SamplingParams:
     def lp_n(self) -> int:
         """The request's ``top_n`` of :func:`ops.token_logprobs`: -1 without logprobs."""
         return self.top_logprobs if self.logprobs else -1
+
+
+class SchemaSlots:
+    """The device pool of compiled JSON-schema automata (ops.json_schema) and its bookkeeping.
+    ``acquire`` gives a request the slot that already holds its schema, or uploads the tables
+    into the least recently used slot that no running request references; None: every slot is
+    pinned by running requests on other schemas, the request waits.  A pure function of the
+    sequence of acquire / release calls (ties: the lowest slot)."""
+
+    def __init__(self, n_slots: int, device):
+        from ..ops import json_schema as J
+
+        self.pool = J.pool_new(n_slots, device)
+        self.n = n_slots
+        self.keys: list = [None] * n_slots
+        self.refs = [0] * n_slots
+        self.used = [0] * n_slots
+        self.clock = 0
+        self.uploads = 0
+
+    def acquire(self, cs) -> int | None:
+        from ..ops import json_schema as J
+
+        self.clock += 1
+        if cs.key in self.keys:
+            slot = self.keys.index(cs.key)
+        else:
+            free = [i for i in range(self.n) if self.refs[i] == 0]
+            if not free:
+                return None
+            slot = min(free, key=lambda i: (self.used[i], i))
+            J.pool_put(self.pool, slot, cs)       # on the current stream, before the next launch
+            self.keys[slot] = cs.key
+            self.uploads += 1
+        self.refs[slot] += 1
+        self.used[slot] = self.clock
+        return slot
+
+    def release(self, slot: int | None) -> None:
+        if slot is not None and self.refs[slot] > 0:
+            self.refs[slot] -= 1
 
 
 @dataclass
@@ -329,6 +400,10 @@ class _DecodeGraph:
         # not constrained); only the constrained graphs touch it
         self.gstate = torch.zeros(bp, dtype=torch.int64, device=dev)
         self.constrained = False
+        # JSON-schema rows: gstate 0 and a non-zero word here (ops.json_schema: DFA state,
+        # whitespace run, the slot of the engine's table pool); only the schema graphs touch it
+        self.sstate = torch.zeros(bp, dtype=torch.int64, device=dev)
+        self.schema = False
         # cascade decode: block ids / length of the prompt prefix every row shares
         self.shared_table = torch.zeros(eng.max_blocks_per_seq, dtype=torch.int32, device=dev)
         self.shared_len = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -357,7 +432,7 @@ class _DecodeGraph:
         g.bp = bp
         for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
                      "top_k", "top_p", "min_p", "seed", "out", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen",
-                     "lp_n", "lp", "lp_top_ids", "lp_top", "gstate"):
+                     "lp_n", "lp", "lp_top_ids", "lp_top", "gstate", "sstate"):
             setattr(g, name, getattr(master, name)[:bp])
         g.shared_table, g.shared_len = master.shared_table, master.shared_len
         g.order = torch.arange(bp, dtype=torch.int32, device=master.tokens.device)
@@ -368,6 +443,7 @@ class _DecodeGraph:
         g.penalized = False
         g.logprobs = False
         g.constrained = False
+        g.schema = False
         g.seeded = g.min_p_on = False
         g.groups_fit = master.groups_fit
         g.hkv = master.hkv
@@ -463,6 +539,10 @@ class LLMEngine:
         self._graphs: dict[tuple, _DecodeGraph] = {}
         self._graphs_min_p: dict[tuple, _DecodeGraph] = {}   # the static min_p flavours (_get_graph)
         self._graphs_json: dict[tuple, _DecodeGraph] = {}    # the static constrained flavours
+        self._graphs_schema: dict[tuple, _DecodeGraph] = {}  # the static JSON-schema flavours
+        # JSON-schema structured outputs: the device pool of compiled automata, one per slot at a
+        # fixed address (captured graphs see static pointers), and who holds which slot
+        self.schema_slots = SchemaSlots(int(os.environ.get("DOCQA_SCHEMA_SLOTS", "8")), self.device)
         # grammar-constrained decoding: the vocabulary's bytes (set_vocab_bytes)
         self.vocab_bytes: list | None = None
         self._grammar = None      # (tok_off int32 [V + 1], tok_bytes uint8, table int16) on the device
@@ -696,6 +776,17 @@ class LLMEngine:
 
         return grammar.replay(out, self.vocab_bytes, self.cfg.eos_token_id)
 
+    def row_states(self, params: SamplingParams, out: list, slot: int | None) -> tuple[int, int]:
+        """(gstate, sstate) of a request that has emitted ``out``: a plain-JSON row carries the
+        JSON automaton's state and sstate 0, a schema row gstate 0 and its schema's word in table
+        slot ``slot``, every other row (0, 0) -- so each kernel pair skips the other's rows."""
+        if params.schema_constrained:
+            from ..ops import json_schema as J
+
+            return 0, J.replay(params.compiled_schema, out, self.vocab_bytes, self.cfg.eos_token_id,
+                               J.start_state(slot))
+        return (self.grammar_state(out) if params.constrained else 0), 0
+
     def _pick_constrained(self, logits, g: _DecodeGraph):
         """The constrained flavours' pick from ``logits`` (the LM head's, a vocab shard at TP > 1):
         the rows' grammar mask over the gathered logits, the flavour's pick on the masked rows
@@ -709,6 +800,9 @@ class LLMEngine:
         R = full.shape[0]   # the first-token pick covers the batch's rows, a step the bucket's
         raw = full.clone() if g.logprobs else None
         ops.grammar_mask(full, V, g.gstate[:R], off, data, table, eos, g.valid[:R])
+        if g.schema:
+            # the schema flavours: rows with a schema word walk the table of their pool slot
+            ops.schema_mask(full, V, g.sstate[:R], off, data, self.schema_slots.pool, eos, g.valid[:R])
         if g.greedy:
             if g.penalized:
                 nxt = self._penalized_greedy(logits, g, full=full)
@@ -730,21 +824,26 @@ class LLMEngine:
         if raw is not None:
             ops.token_logprobs(raw, V, nxt, g.lp_n[:R], g.lp[:R], g.lp_top_ids[:R], g.lp_top[:R])
         ops.grammar_advance(g.gstate[:R], nxt, off, data, table, eos, g.valid[:R])
+        if g.schema:
+            ops.schema_advance(g.sstate[:R], nxt, off, data, self.schema_slots.pool, eos, g.valid[:R])
         return nxt
 
     def _get_graph(self, bp: int, greedy: bool, cascade: bool = False, fit: bool = True,
                    penalized: bool = False, logprobs: bool = False, min_p: bool = False,
-                   constrained: bool = False) -> _DecodeGraph:
-        """``min_p``: the sampled flavour whose pick is ops.sample_tokens -- graphs of their own
+                   constrained: bool = False, schema: bool = False) -> _DecodeGraph:
+        """``schema``: the JSON-schema flavours (the constrained ones plus the schema pair).
+        ``min_p``: the sampled flavour whose pick is ops.sample_tokens -- graphs of their own
         under the same key, so the key and the graphs without min_p stay what they were.
         ``constrained``: the grammar flavours, kept apart the same way."""
         fit = fit or self.max_blocks_per_seq <= ops.GROUP_MAX_BLOCKS
         key = (bp, greedy, cascade, fit, penalized, logprobs)
-        graphs = self._graphs_json if constrained else self._graphs_min_p if min_p else self._graphs
+        graphs = self._graphs_schema if schema else self._graphs_json if constrained else \
+            self._graphs_min_p if min_p else self._graphs
         g = graphs.get(key)
         if g is None:
             g = _DecodeGraph(self, bp)
-            g.constrained = constrained
+            g.constrained = constrained or schema
+            g.schema = schema
             g.min_p_on = min_p
             g.greedy = greedy
             g.penalized = penalized
@@ -920,7 +1019,7 @@ class LLMEngine:
                 tunable.set_rotating_buffer_size(rot)
         # the eager warm-up step advances the slot state (and the penalised flavours' rings)
         state = ((g.tokens, g.positions, g.context_lens) + ((g.hist, g.hist_n) if g.penalized else ())
-                 + ((g.gstate,) if g.constrained else ()))
+                 + ((g.gstate,) if g.constrained else ()) + ((g.sstate,) if g.schema else ()))
         saved = [t.clone() for t in state]
         try:
             s = torch.cuda.Stream()
@@ -1117,6 +1216,13 @@ class LLMEngine:
             penalized = not params.neutral
             want_lp = params.logprobs
             constrained = params.constrained
+            schema_slot = None
+            if params.schema_constrained:
+                # the steps below are all enqueued before this returns and a later upload into
+                # the slot is ordered behind them on the stream: the slot is held only until then
+                schema_slot = self.schema_slots.acquire(params.compiled_schema)
+                if schema_slot is None:
+                    raise RuntimeError("every schema table slot is held by a running request")
             t0 = time.perf_counter()
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if cuda else None
             if cuda:
@@ -1137,7 +1243,8 @@ class LLMEngine:
             fit = self.groups_fit([n + params.max_new_tokens for n in lens])
             grouped = nshared > 0 or self.group_without_prefix(B, fit)
             g = self._get_graph(_bucket(B, self.max_batch) if self.use_graphs else B, greedy, grouped, fit,
-                                penalized, want_lp, min_p=not greedy and params.min_p > 0, constrained=constrained)
+                                penalized, want_lp, min_p=not greedy and params.min_p > 0, constrained=constrained,
+                                schema=params.schema_constrained)
             if grouped:
                 g.shared_len.fill_(0)
             if nshared:
@@ -1174,8 +1281,11 @@ class LLMEngine:
                 from ..ops import grammar
 
                 gs = torch.zeros(g.bp, dtype=torch.int64)
-                gs[:B] = grammar.START_STATE
+                ss = torch.zeros(g.bp, dtype=torch.int64)
+                gs[:B], ss[:B] = self.row_states(params, [], schema_slot)
                 _upload(g.gstate, gs)
+                if params.schema_constrained:
+                    _upload(g.sstate, ss)
             if want_lp:
                 # every row of the batch asks for the same; the bucket's padding slots for nothing
                 ln = torch.full((g.bp,), -1, dtype=torch.int32)
@@ -1260,6 +1370,9 @@ class LLMEngine:
         except BaseException:
             self.release(r)
             raise
+        finally:
+            if params.schema_constrained:
+                self.schema_slots.release(schema_slot)
         self.stats.prompt_tokens += sum(lens)
         self.stats.generated_tokens += B * params.max_new_tokens
         return Launched(r, host, ev, params, t0, t1, ar_err, *(glp or ()))

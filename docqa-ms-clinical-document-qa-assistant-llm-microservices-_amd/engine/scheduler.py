@@ -93,6 +93,8 @@ class Request:
     # key of the request's sampling stream (ops.seeded_uniform): params.seed, or a random one of
     # its own drawn at submission -- never written back to ``params``, which callers share
     seed: int = 0
+    # the request's slot of the engine's schema table pool while it is admitted (None: none held)
+    schema_slot: int | None = None
 
 
 _SEED_RNG = random.SystemRandom()
@@ -176,6 +178,7 @@ class ContinuousEngine:
         self.reserve_ahead = int(os.environ.get("DOCQA_RESERVE_AHEAD", str(engine.block_size)))
         self.preempted = 0
         self.kv_blocked = 0       # admissions deferred because the KV pool was out of blocks
+        self.schema_blocked = 0   # admissions deferred because every schema table slot was pinned
         self.generated = 0        # tokens emitted to requests
         self.completed = 0        # requests finished
         self.completed_short = 0  # ... of them before max_new_tokens (EOS)
@@ -326,6 +329,7 @@ class ContinuousEngine:
             seen.add(id(r))
             self.eng.kv.allocator.free(r.blocks)
             r.blocks = []
+            self._release_schema(r)
             if not r.future.done():
                 r.future.set_exception(e)
         self.running = []
@@ -417,6 +421,13 @@ class ContinuousEngine:
                     break
                 if r.orig_len < 0:
                     r.orig_len = len(r.prompt)
+                if r.params.schema_constrained and r.schema_slot is None:
+                    # a table slot first: when running requests on other schemas pin every slot
+                    # the request stays queued until one retires, as under KV pressure
+                    r.schema_slot = eng.schema_slots.acquire(r.params.compiled_schema)
+                    if r.schema_slot is None:
+                        self.schema_blocked += 1
+                        break
                 remaining = r.params.max_new_tokens - r.gen_base
                 gen = min(remaining, self.reserve_ahead) if self.preempt else remaining
                 try:
@@ -425,6 +436,7 @@ class ContinuousEngine:
                 except MemoryError:
                     # can never fit: nothing else holds KV (running rows, prompts being
                     # chunk-prefilled, lagged completions) to free -- fail, don't stall
+                    self._release_schema(r)
                     if self._occupied() == 0 and not admitted:
                         need = eng.kv.blocks_for(len(r.prompt) + gen)
                         self.waiting.popleft().future.set_exception(MemoryError(
@@ -497,12 +509,14 @@ class ContinuousEngine:
             for r in adm:
                 eng.release(r.res)
                 alloc.free(r.blocks)
+                self._release_schema(r)
                 r.future.set_exception(RuntimeError("TP collective failed during prefill"))
             raise
         except Exception as e:  # noqa: BLE001
             for r in adm:
                 eng.release(r.res)
                 alloc.free(r.blocks)
+                self._release_schema(r)
                 r.future.set_exception(e)
             return
         eng.register_prefixes([r.prompt for r in adm], [r.blocks for r in adm], [r.res.keys[0] if r.res.keys else None
@@ -716,8 +730,9 @@ class ContinuousEngine:
         lpn = torch.tensor([r.params.lp_n for r in reqs], dtype=torch.int32)   # -1: did not ask
         # grammar: the automaton after the request's output so far -- the first token, and after a
         # preemption every token already folded into the resumed prompt; 0: not constrained
-        gst = torch.tensor([self.eng.grammar_state(r.out) if r.params.constrained else 0 for r in reqs],
-                           dtype=torch.int64)
+        # a schema row: 0 there and its schema's word (in its table slot) in sstate
+        gst, sst = (torch.tensor(v, dtype=torch.int64) for v in
+                    zip(*[self.eng.row_states(r.params, r.out, r.schema_slot) for r in reqs]))
         for i, r in enumerate(reqs):
             if not r.params.neutral:
                 hist[i], hn[i] = ring_of(self._stream(r), W)
@@ -755,6 +770,7 @@ class ContinuousEngine:
         m.freq_pen[sl].copy_(pen[:, 2].contiguous().to(dev, non_blocking=True))
         m.lp_n[sl].copy_(lpn.to(dev, non_blocking=True))
         m.gstate[sl].copy_(gst.to(dev, non_blocking=True))
+        m.sstate[sl].copy_(sst.to(dev, non_blocking=True))
         self.running.extend(reqs)
         self._version += 1
 
@@ -802,9 +818,12 @@ class ContinuousEngine:
             if keep:
                 full = full.clone()
             off, data, table = self.eng._grammar
-            gst = torch.tensor([self.eng.grammar_state(r.out) if r.params.constrained else 0 for r in reqs],
-                               dtype=torch.int64, device=dev)
+            gst, sst = (torch.tensor(v, dtype=torch.int64, device=dev) for v in
+                        zip(*[self.eng.row_states(r.params, r.out, r.schema_slot) for r in reqs]))
             ops.grammar_mask(full, self.eng.cfg.vocab_size, gst, off, data, table, self.eng.cfg.eos_token_id)
+            if any(p.schema_constrained for p in params):
+                ops.schema_mask(full, self.eng.cfg.vocab_size, sst, off, data, self.eng.schema_slots.pool,
+                                self.eng.cfg.eos_token_id)
             if all(p.temperature <= 0.0 and p.neutral for p in params):
                 return ops.argmax(full).tolist()
         pen = None
@@ -832,16 +851,20 @@ class ContinuousEngine:
         return ops.sample_tokens(full, self.eng.cfg.vocab_size, it, tk, tp, mp, seed=seed, index=index).tolist()
 
     def _graph(self, bp: int, greedy: bool, cascade: bool, fit: bool = True,
-               penalized: bool = False, logprobs: bool = False, constrained: bool = False) -> _DecodeGraph:
+               penalized: bool = False, logprobs: bool = False, constrained: bool = False,
+               schema: bool = False) -> _DecodeGraph:
         """``constrained``: the grammar flavours, under keys one entry longer -- the other
-        flavours' keys and graphs stay what they were."""
+        flavours' keys and graphs stay what they were.  ``schema``: the flavours of a step with a
+        JSON-schema row, which launch the grammar pair and the schema pair."""
         fit = fit or self._master.groups_fit
-        key = (bp, greedy, cascade, fit, penalized, logprobs) + (("json",) if constrained else ())
+        key = (bp, greedy, cascade, fit, penalized, logprobs) + (("schema",) if schema else ("json",) if constrained
+                                                                   else ())
         g = self._graphs.get(key)
         if g is None:
             g = _DecodeGraph.view_of(self._master, bp)
             g.greedy, g.cascade, g.groups_fit = greedy, cascade, fit
-            g.constrained = constrained
+            g.constrained = constrained or schema
+            g.schema = schema
             g.penalized = penalized
             g.logprobs = logprobs
             g.seeded = True      # this scheduler's graphs sample per slot from (seed, position)
@@ -895,6 +918,7 @@ class ContinuousEngine:
             v = max(self.prefilling, key=lambda r: (r.t_arrival, r.rid))
             self.eng.kv.allocator.free(v.blocks)
             v.blocks, v.res, v.cached, v.filled = [], None, 0, 0
+            self._release_schema(v)
             self.prefilling = [r for r in self.prefilling if r is not v]
             v.preemptions += 1
             self.preempted += 1
@@ -909,6 +933,7 @@ class ContinuousEngine:
             self.eng.kv.allocator.free(v.blocks)
             v.blocks = []
             v.done = True
+            self._release_schema(v)
             if not v.future.done():
                 v.future.set_exception(MemoryError("KV cache exhausted by a single request"))
             self._compact([])
@@ -916,6 +941,7 @@ class ContinuousEngine:
             return
         self.eng.kv.allocator.free(v.blocks)
         v.blocks, v.res, v.cached = [], None, 0
+        self._release_schema(v)
         keep = [i for i, r in enumerate(self.running) if r is not v]
         self._compact(keep)
         v.prompt = v.prompt[:v.orig_len] + list(v.out)
@@ -941,7 +967,9 @@ class ContinuousEngine:
         want_lp = any(r.params.logprobs for r in self.running)
         # any running row is grammar-constrained: the flavour that masks and advances (those rows only)
         constrained = any(r.params.constrained for r in self.running)
-        g = self._graph(bp, greedy, grouped, fit, penalized, want_lp, constrained)
+        # any running row has a JSON schema: the flavour that also runs the schema pair
+        schema = any(r.params.schema_constrained for r in self.running)
+        g = self._graph(bp, greedy, grouped, fit, penalized, want_lp, constrained, schema)
         if eng.lpt:
             # re-rank only when the running set changed (admission / retirement)
             eng.set_order(g, [len(r.prompt) + len(r.out) for r in self.running], key=self._version)
@@ -1059,8 +1087,14 @@ class ContinuousEngine:
                 r.stop_check = None
         return False
 
+    def _release_schema(self, r: Request) -> None:
+        if r.schema_slot is not None:
+            self.eng.schema_slots.release(r.schema_slot)
+            r.schema_slot = None
+
     def _retire(self, r: Request) -> None:
         self.completed += 1
+        self._release_schema(r)
         self.completed_short += len(r.out) < r.params.max_new_tokens
         self.eng.kv.allocator.free(r.blocks)
         r.blocks = []
@@ -1074,11 +1108,12 @@ class ContinuousEngine:
             idx = torch.tensor(keep, dtype=torch.long, device=m.tokens.device)
             for name in ("tokens", "positions", "context_lens", "valid", "block_tables", "inv_temp",
                          "top_k", "top_p", "min_p", "seed", "hist", "hist_n", "last_n", "rep_pen", "pres_pen", "freq_pen", "lp_n",
-                         "gstate"):
+                         "gstate", "sstate"):
                 t = getattr(m, name)
                 t[:k] = t[idx]
         m.lp_n[k:n].fill_(-1)
         m.gstate[k:n].zero_()
+        m.sstate[k:n].zero_()
         m.valid[k:n].zero_()
         m.context_lens[k:n].zero_()
         m.positions[k:n].zero_()

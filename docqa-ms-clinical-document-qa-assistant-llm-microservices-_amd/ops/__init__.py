@@ -1509,6 +1509,33 @@ def grammar_advance(state, nxt, tok_off, tok_bytes, table, eos_id: int, valid=No
     ref.grammar_advance(state, nxt, tok_off, tok_bytes, table, int(eos_id), valid)
 
 
+def schema_mask(logits, n_valid: int, sstate, tok_off, tok_bytes, pool, eos_id: int, valid=None) -> None:
+    """JSON-schema structured outputs (:mod:`docqa_amd.ops.json_schema`,
+    csrc/kernels/grammar_schema.hip): :func:`grammar_mask`'s contract with a per-row automaton.
+    In place on bf16 / fp32 logits [R, ld], every row with ``sstate != 0`` (int64 [R]: DFA state,
+    whitespace run and table slot) and ``valid != 0`` gets ``-inf`` in each column ``t < n_valid``
+    whose token is not allowed: allowed is a token with bytes that walk from the row's state
+    through the ``cls`` / ``trans`` tables of the row's slot of ``pool`` (uint8 [slots,
+    json_schema.SLOT_BYTES]) without a reject, or ``t == eos_id`` in DONE.  A slot past the pool
+    or with a header out of range allows nothing.  Allowed columns, columns at or past ``n_valid``
+    and skipped rows are left bit for bit; no logit is read."""
+    if _gpu(logits):
+        _native().schema_mask(logits, int(n_valid), sstate, tok_off, tok_bytes, pool, int(eos_id), valid)
+        return
+    ref.schema_mask(logits, int(n_valid), sstate, tok_off, tok_bytes, pool, int(eos_id), valid)
+
+
+def schema_advance(sstate, nxt, tok_off, tok_bytes, pool, eos_id: int, valid=None) -> None:
+    """In place on ``sstate`` int64 [R]: the word after the bytes of the picked token ``nxt``
+    (int64 [R]) walked through the row's slot of ``pool``.  Word 0 stays 0, DONE stays DONE, EOS
+    leaves the word as it is, and so does a token that would be rejected or has no bytes.  GPU
+    and CPU agree as int64."""
+    if _gpu(sstate):
+        _native().schema_advance(sstate, nxt, tok_off, tok_bytes, pool, int(eos_id), valid)
+        return
+    ref.schema_advance(sstate, nxt, tok_off, tok_bytes, pool, int(eos_id), valid)
+
+
 def decode_advance_hist(nxt, out, tokens, positions, context_lens, valid, hist, hist_n) -> None:
     """:func:`decode_advance`, and the valid rows' new token joins their ring:
     hist[i, hist_n[i] % W] <- nxt[i], hist_n[i] += 1."""

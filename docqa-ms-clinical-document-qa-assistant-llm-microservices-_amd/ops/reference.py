@@ -704,3 +704,119 @@ def grammar_advance(state, nxt, tok_off, tok_bytes, table, eos_id: int, valid=No
                 break
         if s >= 0:
             state[r] = s
+
+
+# ----------------------------------------------------------------------------- JSON schema (format: a schema)
+def _schema_allowed(word: int, n: int, off, data, tables, eos_id: int):
+    """bool [n]: which of the tokens [0, n) a row with state ``word`` (non-zero) may emit; ``tables``
+    is the (cls, trans) of the row's pool slot, or None (nothing is allowed)."""
+    return _schema_walk(word, n, off, data, tables, eos_id)[0]
+
+
+def _schema_walk(word: int, n: int, off, data, tables, eos_id: int):
+    """(allowed bool [n], after int64 [n]) of a row with state ``word`` (non-zero): which of the
+    tokens [0, n) it may emit, and its word after each of them (``word`` itself where the token
+    leaves it unchanged: not allowed, EOS, no bytes) -- every token walked at once, one byte
+    position per numpy pass over the tokens still alive."""
+    import numpy as np
+
+    from . import json_schema as J
+
+    allowed = np.zeros(n, dtype=bool)
+    after = np.full(n, word, dtype=np.int64)
+    if J.is_done(word):
+        if 0 <= eos_id < n:
+            allowed[eos_id] = True
+        return allowed, after
+    st0, ws0, slot = J.unpack(word)
+    if tables is None or st0 >= tables[1].shape[0]:
+        return allowed, after
+    cls, trans = tables
+    ns, nc = trans.shape
+    flat = trans.reshape(-1).astype(np.int64)
+    nt = min(n, len(off) - 1)
+    lens = (off[1:nt + 1] - off[:nt]).astype(np.int64)
+    idx = np.nonzero(lens > 0)[0]
+    st = np.full(idx.size, st0, dtype=np.int64)
+    ws = np.full(idx.size, ws0, dtype=np.int64)
+    j = 0
+    while idx.size:
+        c = cls[data[off[idx] + j]].astype(np.int64)
+        ok = c < nc
+        e = flat[st * nc + np.minimum(c, nc - 1)]
+        nxt, is_ws = e & J.NEXT_MASK, (e & J.WS_FLAG) != 0
+        ok &= (e != 0) & (nxt < ns) & ~(is_ws & (ws >= J.WS_CAP))
+        ws = np.where(is_ws, ws + 1, 0)
+        st = np.minimum(nxt, ns - 1)
+        j += 1
+        ended = ok & (lens[idx] == j)
+        allowed[idx[ended]] = True
+        after[idx[ended]] = st[ended] | ws[ended] << 16 | slot << 21
+        go = ok & ~ended
+        idx, st, ws = idx[go], st[go], ws[go]
+    if 0 <= eos_id < n:
+        allowed[eos_id] = False      # EOS only in DONE, whatever bytes it has
+        after[eos_id] = word
+    return allowed, after
+
+
+def schema_mask(logits, n_valid: int, sstate, tok_off, tok_bytes, pool, eos_id: int, valid=None) -> None:
+    """In place: -inf into every column t < n_valid of a schema row (word != 0, valid != 0) whose
+    token the automaton of the row's pool slot does not allow in the row's state
+    (ops.json_schema); nothing else is written.  Rows with the same word share one walk."""
+    from . import json_schema as J
+
+    off, data, pool_np = tok_off.cpu().numpy(), tok_bytes.cpu().numpy(), pool.cpu().numpy()
+    words = sstate.tolist()
+    cache: dict = {}
+    for r in range(logits.shape[0]):
+        w = words[r]
+        if w == 0 or (valid is not None and int(valid[r]) == 0):
+            continue
+        if w not in cache:
+            tables = J.pool_tables(pool_np, J.unpack(w)[2])
+            cache[w] = torch.from_numpy(~_schema_allowed(w, int(n_valid), off, data, tables, int(eos_id)))
+        logits[r, :n_valid].masked_fill_(cache[w].to(logits.device), -math.inf)
+
+
+def schema_advance(sstate, nxt, tok_off, tok_bytes, pool, eos_id: int, valid=None) -> None:
+    """In place on sstate int64 [R]: the word after the bytes of token nxt[i]; 0 and DONE stay,
+    EOS and a token that would be rejected (or has no bytes) leave the word unchanged."""
+    from . import json_schema as J
+
+    off, data, pool_np = tok_off.cpu().numpy(), tok_bytes.cpu().numpy(), pool.cpu().numpy()
+    words, toks = sstate.tolist(), nxt.tolist()
+    tabs: dict = {}
+    # many rows in one word (a test's sweep over the vocabulary): one walk of every token
+    import collections
+
+    walked = {w: None for w, c in collections.Counter(words).items() if c > 8 and w != 0 and not J.is_done(w)}
+    for r, (w, t) in enumerate(zip(words, toks)):
+        if w == 0 or J.is_done(w) or t == eos_id or (valid is not None and int(valid[r]) == 0):
+            continue
+        if w in walked:
+            if walked[w] is None:
+                walked[w] = _schema_walk(w, len(off) - 1, off, data, J.pool_tables(pool_np, J.unpack(w)[2]),
+                                         int(eos_id))[1]
+            if 0 <= t < len(off) - 1:
+                sstate[r] = int(walked[w][t])
+            continue
+        if not 0 <= t < len(off) - 1 or off[t + 1] == off[t]:
+            continue
+        st, ws, slot = J.unpack(w)
+        if slot not in tabs:
+            got = J.pool_tables(pool_np, slot)
+            tabs[slot] = None if got is None else (got[0].tolist(), got[1].astype("int32").tolist())
+        if tabs[slot] is None or st >= len(tabs[slot][1]):
+            continue
+        cls, trans = tabs[slot]
+        nc = len(trans[0])
+        for b in data[off[t]:off[t + 1]].tolist():
+            c = cls[b]
+            e = trans[st][c] if c < nc else 0
+            if e == 0 or (e & J.NEXT_MASK) >= len(trans) or (e & J.WS_FLAG and ws >= J.WS_CAP):
+                st = -1
+                break
+            st, ws = e & J.NEXT_MASK, (ws + 1 if e & J.WS_FLAG else 0)
+        if st >= 0:
+            sstate[r] = J.pack(st, ws, slot)

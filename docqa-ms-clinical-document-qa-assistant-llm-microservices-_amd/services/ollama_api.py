@@ -46,9 +46,23 @@ step masks the tokens that would leave llama.cpp's json.gbnf with an object root
 only once the object has closed), so whenever done_reason is "stop" by EOS the text parses with
 json.loads; "length" means num_predict cut the object short, as with Ollama.  Two caps keep a
 model from looping: a run of more than 16 whitespace characters outside strings and nesting deeper
-than 32 are not generated.  A JSON-schema OBJECT as "format" is accepted and constrains to a JSON
-object, but the schema itself is NOT enforced yet (Ollama compiles it to a grammar; here that is
-a different transition table, left as the follow-up).  Any other "format" is a 400 {"error"}.
+than 32 are not generated.  A JSON-schema OBJECT as "format" (what ChatOllama's
+with_structured_output and format=Model.model_json_schema() send) is compiled to a byte-level
+automaton of its own (ops/json_schema.py, csrc/kernels/grammar_schema.hip) and ENFORCED the same
+way: whenever done_reason is "stop" by EOS the text parses and validates against the schema;
+"length" means num_predict cut it short.  Supported: type (object array string integer number
+boolean null, or a list), properties / required (additionalProperties absent or false), items /
+minItems / maxItems, enum / const of scalars, $ref into #/$defs or #/definitions, anyOf / oneOf,
+allOf with one member, and the annotations title description default examples $schema $id
+$comment deprecated readOnly writeOnly.  Anything else -- free-form sub-values (an object without
+properties, additionalProperties true or a schema), recursive $ref, minLength / maxLength /
+pattern / format, minimum / maximum / multipleOf -- is a 400 {"error"} that names the keyword by
+its JSON pointer, as is a schema too large for a table slot.  Deviations: the root must be an
+object; properties are generated in DECLARED order (required ones always, the others may be
+skipped) and no other key; oneOf is a union (exclusivity is not enforced); integers have at most
+16 digits, fractions 16 and exponents 3, so a row cannot emit digits for ever; whitespace runs
+<= 16 as above.  At most DOCQA_SCHEMA_SLOTS (8) distinct schemas decode at once: a request whose
+schema finds every table slot in use waits in the queue.  Any other "format" is a 400 {"error"}.
 "logprobs" stay the model's own distribution, from the logits before the grammar mask.  "stop" (a string
 or a list) ends the text just before the earliest match with done_reason "stop"; a streamed
 tail that could still grow into a stop string is held back until it is resolved.
@@ -109,9 +123,16 @@ class OllamaGenerateRequest(BaseModel):
     format: object = None
 
 
+def schema_from_request(fmt) -> dict | None:
+    """The request's ``format`` as ``SamplingParams.json_schema``: a JSON-schema object is passed
+    through (``SamplingParams.set_json_schema`` compiles it and raises ValueError with the
+    keyword that is not supported), anything else is no schema."""
+    return fmt if isinstance(fmt, dict) else None
+
+
 def format_from_request(fmt) -> str:
     """The request's ``format`` as ``SamplingParams.format``: absent / null / "" is off, "json"
-    and a JSON-schema object constrain to a JSON object (the schema is not enforced yet).  Raises
+    and a JSON-schema object (:func:`schema_from_request`) constrain the output.  Raises
     ValueError (the routes answer 400) on anything else."""
     if fmt is None or fmt == "":
         return ""
@@ -232,6 +253,7 @@ def register(app: FastAPI, settings, metrics) -> None:
         try:
             params = sampling_from_options(options, settings, pipe.engine.max_context, len(ids))
             params.format = format_from_request(fmt)
+            params.set_json_schema(schema_from_request(fmt))
             if params.constrained:
                 if getattr(getattr(batcher, "engine", None), "mixed", False):
                     raise ValueError('format "json" is not served with mixed steps (DOCQA_MIXED_PREFILL=1)')

@@ -104,7 +104,7 @@ class DynamicBatcher:
                 p = b[1]["params"]
                 groups.setdefault((p.max_new_tokens, p.temperature, p.top_k, p.top_p, p.min_p, p.stop_on_eos, p.seed,
                                    p.repeat_penalty, p.repeat_last_n, p.presence_penalty, p.frequency_penalty,
-                                   p.logprobs, p.top_logprobs, p.format), []).append(b)
+                                   p.logprobs, p.top_logprobs, p.format, p.schema_key), []).append(b)
             for grp in groups.values():
                 p = grp[0][1]["params"]
                 if p.logprobs:
