@@ -1809,6 +1809,48 @@ std::tuple<at::Tensor, at::Tensor> knn(const at::Tensor& xb, const at::Tensor& x
   return {out_d, out_i};
 }
 
+// exact search among the rows whose (tag, day) satisfy the query's scope row (knn.hip)
+std::tuple<at::Tensor, at::Tensor> knn_scoped(const at::Tensor& xb, const at::Tensor& xb_norms,
+                                              const at::Tensor& tags, const at::Tensor& days,
+                                              const at::Tensor& xq, const at::Tensor& scope, int64_t k,
+                                              bool inner_product, int64_t id_offset) {
+  CHECK_GPU(xb); CHECK_GPU(tags); CHECK_GPU(days); CHECK_GPU(xq); CHECK_GPU(scope);
+  CHECK_CONTIG(xb); CHECK_CONTIG(tags); CHECK_CONTIG(days); CHECK_CONTIG(xq); CHECK_CONTIG(scope);
+  TORCH_CHECK(xq.scalar_type() == at::kFloat, "queries must be fp32");
+  const bool bf = xb.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(bf || xb.scalar_type() == at::kFloat, "database must be fp32 or bf16");
+  TORCH_CHECK(xb.dim() == 2 && xq.dim() == 2 && xb.size(1) == xq.size(1), "dimension mismatch");
+  TORCH_CHECK(k >= 1 && docqa_knn_kpad(k) > 0, "k must be in [1, 64]");
+  const int N = xb.size(0), d = xb.size(1), nq = xq.size(0);
+  TORCH_CHECK(tags.scalar_type() == at::kInt && days.scalar_type() == at::kInt && tags.numel() == N &&
+              days.numel() == N, "knn_scoped: tags / days must be int32 [N]");
+  TORCH_CHECK(scope.scalar_type() == at::kInt && scope.dim() == 2 && scope.size(0) == nq && scope.size(1) == 4,
+              "knn_scoped: scope must be int32 [nq, 4]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(scope.data_ptr()) % 16 == 0, "knn_scoped: scope must be 16-byte aligned");
+  c10::DeviceGuard g(xb.device());
+  auto out_d = at::empty({nq, k}, xq.options());
+  auto out_i = at::empty({nq, k}, xq.options().dtype(at::kLong));
+  if (N == 0 || nq == 0) {
+    out_d.fill_(inner_product ? -3.4028234663852886e38 : 3.4028234663852886e38);
+    out_i.fill_(-1);
+    return {out_d, out_i};
+  }
+  if (!inner_product) {
+    CHECK_GPU(xb_norms); CHECK_CONTIG(xb_norms);
+    TORCH_CHECK(xb_norms.scalar_type() == at::kFloat && xb_norms.numel() == N, "knn_scoped: norms must be fp32 [N]");
+  }
+  const int nblk = docqa_knn_workspace_blocks(N);
+  const int kp = docqa_knn_kpad(k);
+  auto ws_d = at::empty({nq, nblk, kp}, xq.options());
+  auto ws_i = at::empty({nq, nblk, kp}, xq.options().dtype(at::kInt));
+  const float* norms = inner_product ? nullptr : xb_norms.data_ptr<float>();
+  CHECK_RC(docqa_knn_scoped(xb.data_ptr(), norms, tags.data_ptr<int>(), days.data_ptr<int>(), N, d, bf ? 1 : 0,
+                            xq.data_ptr<float>(), scope.data_ptr<int>(), nq, k, inner_product ? 1 : 0,
+                            ws_d.data_ptr<float>(), ws_i.data_ptr<int>(), nblk, out_d.data_ptr<float>(),
+                            out_i.data_ptr<int64_t>(), id_offset, stream()), "knn_scoped");
+  return {out_d, out_i};
+}
+
 // IVF coarse quantizer, wide probes: int64 [nq, nprobe] nearest centroids (ascending, ties
 // to the lower id) for nprobe <= 512
 // exact fp32 x @ w^T on the coarse quantizer's MFMA tiles (the IVF-PQ query pre-rotation)
@@ -2072,6 +2114,8 @@ TORCH_LIBRARY(docqa, m) {
         "float scale, bool causal) -> Tensor");
   m.def("knn(Tensor xb, Tensor xb_norms, Tensor xq, int k, bool inner_product, int id_offset) "
         "-> (Tensor, Tensor)");
+  m.def("knn_scoped(Tensor xb, Tensor xb_norms, Tensor tags, Tensor days, Tensor xq, Tensor scope, int k, "
+        "bool inner_product, int id_offset) -> (Tensor, Tensor)");
   m.def("pool_l2(Tensor h, Tensor cu_seqlens, bool mean, bool normalize) -> Tensor");
   m.def("coarse_probes(Tensor xq, Tensor cent, Tensor cnorm, int nprobe) -> Tensor");
   m.def("fp32_gemm_nt(Tensor x, Tensor w) -> Tensor");
@@ -2190,6 +2234,7 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("paged_decode", &paged_decode);
   m.impl("flash_prefill", &flash_prefill);
   m.impl("knn", &knn);
+  m.impl("knn_scoped", &knn_scoped);
   m.impl("pool_l2", &pool_l2);
   m.impl("ivfpq_search", &ivfpq_search);
   m.impl("ivfpq_search_pt", &ivfpq_search_pt);

@@ -296,6 +296,12 @@ int docqa_knn_kpad(int k);
 int docqa_knn(const void* xb, const float* norms, int N, int d, int is_bf16, const float* xq,
               int nq, int k, int metric_ip, float* ws_d, int* ws_i, int nblk, float* out_d,
               int64_t* out_i, int64_t id_offset, hipStream_t s);
+// scoped exact search: tags / days int32 [N], scope int32 [nq, 4] = (tag, alt_tag, day_lo,
+// day_hi); workspace and outputs as docqa_knn
+int docqa_knn_scoped(const void* xb, const float* norms, const int* tags, const int* days, int N,
+                     int d, int is_bf16, const float* xq, const int* scope, int nq, int k,
+                     int metric_ip, float* ws_d, int* ws_i, int nblk, float* out_d, int64_t* out_i,
+                     int64_t id_offset, hipStream_t s);
 
 int docqa_ivfpq_search(const float* xq, const float* centroids, const float* pq,
                        const uint8_t* codes, const int64_t* ids, const int64_t* list_off,

@@ -119,6 +119,26 @@ class FlatIndex:
                 nm.record_stream(s)
             return ops.knn(xb[: self.ntotal], nm[: self.ntotal], xq, k, self.metric == "ip", id_offset)
 
+    def search_scoped(self, xq, k: int, cols, scope, id_offset: int = 0):
+        """``search`` among the rows inside each query's scope: ``cols`` the rows'
+        :class:`~docqa_amd.index.scope.ScopeColumns`, ``scope`` int32 [nq, 4] (its
+        ``scope_rows``).  Exact; covers rows ``[0, min(ntotal, cols.n))``."""
+        xq = torch.as_tensor(xq)
+        if xq.dim() == 1:
+            xq = xq[None]
+        xq = xq.to(self.device, dtype=torch.float32)
+        scope = torch.as_tensor(scope).to(self.device, dtype=torch.int32)
+        with self._lock:
+            n = min(self.ntotal, cols.n)      # before the buffers: they only ever grow
+            xb, nm, tags, days = self._xb, self._norms, cols._tags, cols._days
+            if xb.is_cuda:
+                # as in search(): the kernel may run on a side stream while these are dropped
+                s = torch.cuda.current_stream(self.device)
+                for t in (xb, nm, tags, days):
+                    t.record_stream(s)
+            return ops.knn_scoped(xb[:n], nm[:n], tags[:n], days[:n], xq, scope, k, self.metric == "ip",
+                                  id_offset)
+
     def reconstruct(self, i: int) -> np.ndarray:
         return self._xb[i].float().cpu().numpy()
 

@@ -25,6 +25,7 @@ from ..store import metadata_io
 from ..store.segment_log import read_snapshot_marker, tail_frames
 from . import faiss_io
 from .flat import FlatIndex
+from .scope import ScopeColumns
 
 log = logging.getLogger("docqa.index.follower")
 
@@ -44,6 +45,7 @@ class IndexFollower:
         else:
             self.index = FlatIndex(d, "l2", device)
         self.metadata: list[dict] = []
+        self.scopes = ScopeColumns(device)   # row tags / days of the scoped search
         self.poll_s = poll_s
         self.last_seq = 0          # highest WAL sequence applied
         self._marker = None        # snapshot marker the current state is based on
@@ -77,6 +79,7 @@ class IndexFollower:
 
         def swap_meta():
             self.metadata[:] = meta
+            self.scopes.rebuild(self.metadata)
 
         if ivf is not None and hasattr(self.index, "ivf"):
             self.index.replace(xb, before_swap=swap_meta, ivf=ivf)
@@ -103,6 +106,7 @@ class IndexFollower:
             if seq <= self.last_seq:
                 continue
             self.metadata.extend(recs)       # records first: every searchable id resolves
+            self.scopes.extend(self.metadata)
             self.index.add(torch.from_numpy(vecs.copy()))
             self.last_seq = seq
             added += len(recs)

@@ -118,6 +118,12 @@ class IVFPQRefineIndex:
             I = torch.where(I >= 0, I + id_offset, I)
         return D, I
 
+    def search_scoped(self, xq, k: int, cols, scope, id_offset: int = 0):
+        """Scoped search is the exact scan over the stored vectors, trained or not (a scope
+        is usually a sliver of the store: the kernel skips the tiles outside it)."""
+        with self._lock:
+            return self.flat.search_scoped(xq, k, cols, scope, id_offset=id_offset)
+
     def reconstruct(self, i: int) -> np.ndarray:
         return self.flat.reconstruct(i)
 

@@ -213,6 +213,11 @@ class ShardedIndex:
             self._tls.snap = self._ipc.snapshot()
         return D, I
 
+    def search_scoped(self, xq, k: int, cols, scope, id_offset: int = 0):
+        raise NotImplementedError(
+            "Tags would have to agree across ranks, and no service builds a sharded index. "
+            "That belongs with sharding the deployed index.")
+
     def _search(self, xq: torch.Tensor, k: int, **kw):
         nq = xq.shape[0]
         dev = xq.device

@@ -1916,6 +1916,27 @@ def knn(xb, xb_norms, xq, k: int, inner_product: bool = False, id_offset: int = 
     return ref.knn(xb, xb_norms, xq, k, inner_product, id_offset)
 
 
+def knn_scoped(xb, xb_norms, tags, days, xq, scope, k: int, inner_product: bool = False, id_offset: int = 0):
+    """:func:`knn` among the rows whose (tag, day) satisfy the query's scope row: tags / days
+    int32 [N], scope int32 [nq, 4] = (tag, alt_tag, day_lo, day_hi), see
+    ``reference.knn_scoped`` for the predicate.  GPU: the SCOPED instantiations of the fused
+    kernel (csrc/kernels/knn.hip), which skip tiles no query's scope touches.  Shapes outside
+    the kernel's envelope (k > 64, d not a multiple of 8 / 16 for fp32 / bf16 storage, query
+    staging + 512 B of scope rows over 160 KiB of LDS) and ``DOCQA_KNN_SCOPED=0`` (kill
+    switch) take the fp32 reference on the same device instead of failing."""
+    if _gpu(xb) and os.environ.get("DOCQA_KNN_SCOPED", "1") != "0":
+        bf = xb.dtype == torch.bfloat16
+        d = int(xb.shape[1])
+        kp = next((p for p in (4, 8, 16, 32, 64) if k <= p), 0)
+        lds = max(32 * d * (2 if bf else 4), 32 * 8 * kp * 8) + 512
+        if (kp and k >= 1 and (bf or xb.dtype == torch.float32) and d % (16 if bf else 8) == 0
+                and lds <= 160 * 1024):
+            return _native().knn_scoped(xb, xb_norms, tags.int().contiguous(), days.int().contiguous(),
+                                        xq.float().contiguous(), scope.int().contiguous(), k,
+                                        inner_product, id_offset)
+    return ref.knn_scoped(xb, xb_norms, tags, days, xq, scope, k, inner_product, id_offset)
+
+
 def fp32_matmul_nt(x, w):
     """Exact fp32 ``x @ w.T`` on the coarse quantizer's MFMA tiles (coarse.hip) -- the IVF-PQ
     query pre-rotation on the GPU without a library GEMM; torch on the CPU."""

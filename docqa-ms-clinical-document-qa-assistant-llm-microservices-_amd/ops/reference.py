@@ -490,6 +490,42 @@ def knn(xb, xb_norms, xq, k, inner_product, id_offset):
     return D, I
 
 
+def knn_scoped(xb, xb_norms, tags, days, xq, scope, k, inner_product, id_offset):
+    """:func:`knn` among the rows inside each query's scope.  tags / days int32 [N], scope
+    int32 [nq, 4] = (tag, alt_tag, day_lo, day_hi); a row matches iff
+
+        row_tag == alt_tag || ((tag < 0 || row_tag == tag) && day_lo <= row_day && row_day <= day_hi)
+
+    (tag -1 = any, alt_tag -1 = none, 0 = also the knowledge base, exempt from the window;
+    (INT32_MIN, INT32_MAX) = no window; an undated row carries day INT32_MIN).  Slots past
+    the number of matching rows hold -1 and the sentinel distance."""
+    nq = xq.shape[0]
+    N = xb.shape[0]
+    sent = -3.4028234663852886e38 if inner_product else 3.4028234663852886e38
+    D = torch.full((nq, k), sent, dtype=torch.float32, device=xq.device)
+    I = torch.full((nq, k), -1, dtype=torch.long, device=xq.device)
+    if N == 0 or nq == 0:
+        return D, I
+    rt, rd = tags.reshape(-1)[None, :].int(), days.reshape(-1)[None, :].int()
+    sc = scope.int()
+    tag, alt, lo, hi = (sc[:, j:j + 1] for j in range(4))
+    match = (rt == alt) | (((tag < 0) | (rt == tag)) & (lo <= rd) & (rd <= hi))
+    xbf = xb.float()
+    xqf = xq.float()
+    ip = xqf @ xbf.T
+    if inner_product:
+        score = ip.masked_fill(~match, -math.inf)
+        vals, idx = torch.topk(score, min(k, N), dim=1, largest=True)
+    else:
+        norms = xb_norms.float() if xb_norms is not None else (xbf * xbf).sum(1)
+        score = ((xqf * xqf).sum(1, keepdim=True) + norms[None, :] - 2 * ip).masked_fill(~match, math.inf)
+        vals, idx = torch.topk(score, min(k, N), dim=1, largest=False)
+    ok = torch.gather(match, 1, idx)
+    D[:, : vals.shape[1]] = torch.where(ok, vals, torch.full_like(vals, sent))
+    I[:, : idx.shape[1]] = torch.where(ok, idx + id_offset, torch.full_like(idx, -1))
+    return D, I
+
+
 def pool_l2(h, cu_seqlens, mean, normalize):
     cu = cu_seqlens.tolist()
     out = torch.zeros(len(cu) - 1, h.shape[-1], dtype=torch.float32, device=h.device)

@@ -90,6 +90,10 @@ class RAGPipeline:
         self.template = template
         self.max_prompt_tokens = max_prompt_tokens
         self.last_times = StageTimes()
+        # row tags / days of the scoped search (index/scope.py): an IndexFollower's or the
+        # indexer's when one owns the (index, metadata) pair, else built lazily from metadata
+        self.scopes = None
+        self._own_scopes = None
         # token ids of every retrieved chunk, tokenised once: a prompt is then assembled
         # from cached pieces split at paragraph boundaries (the byte-level BPE never merges
         # across a newline pre-token), so only the question is tokenised per request
@@ -118,12 +122,31 @@ class RAGPipeline:
             check()
         return ids
 
-    def retrieve(self, questions: list[str]):
+    def search(self, qemb: torch.Tensor, scopes: list | None = None):
+        """(D, I) of the embedded questions' top-k.  ``scopes``: per question ``None`` or a
+        scope request (index/scope.py: patient_id, from_date, to_date,
+        include_knowledge_base); a batch without any takes the unscoped search, a mixed
+        batch is one scoped launch (``None`` = the any-scope row)."""
+        if scopes is None or all(s is None for s in scopes):
+            return self.index.search(qemb, self.k)
+        if len(scopes) != qemb.shape[0]:
+            raise ValueError("one scope per question")
+        if self.scopes is None:
+            from ..index.scope import ScopeColumns
+
+            self._own_scopes = self.scopes = ScopeColumns(getattr(self.index, "device", qemb.device))
+        if self._own_scopes is self.scopes:     # no follower / indexer keeps it in step
+            if self.scopes.n > len(self.metadata):
+                self.scopes.rebuild(self.metadata)
+            self.scopes.extend(self.metadata)
+        return self.index.search_scoped(qemb, self.k, self.scopes, self.scopes.scope_rows(scopes))
+
+    def retrieve(self, questions: list[str], scopes: list | None = None):
         """(D, I) of the questions' top-k.  On a sharded index the hits are checked for a
         failed cross-rank gather here (one host sync on the search's ids) so no caller can
         use stale peer rows unchecked."""
         q = self.embed(questions)
-        D, I = self.index.search(q, self.k)
+        D, I = self.search(q, scopes)
         if getattr(self.index, "check_gather", None) is not None:
             self._host_ids(I)
         return D, I
@@ -207,7 +230,8 @@ class RAGPipeline:
         return prompts
 
     @torch.inference_mode()
-    def answer_batch(self, questions: list[str], params: SamplingParams | None = None) -> list[Answer]:
+    def answer_batch(self, questions: list[str], params: SamplingParams | None = None,
+                     scopes: list | None = None) -> list[Answer]:
         params = params or SamplingParams(stop_on_eos=True)
         t = StageTimes()
         t0 = time.perf_counter()
@@ -216,7 +240,7 @@ class RAGPipeline:
             self._sync()
         t1 = time.perf_counter()
         with tracing.span("rag.search", n=len(questions), k=self.k):
-            D, I = self.index.search(qemb, self.k)
+            D, I = self.search(qemb, scopes)
             I = self._host_ids(I)  # host needs ids to assemble the prompts
         t2 = time.perf_counter()
         with tracing.span("rag.prompt", n=len(questions)):
@@ -234,12 +258,12 @@ class RAGPipeline:
                               chunk_ids=list(ids)))
         return res
 
-    def answer(self, question: str, params: SamplingParams | None = None) -> Answer:
-        return self.answer_batch([question], params)[0]
+    def answer(self, question: str, params: SamplingParams | None = None, scope: dict | None = None) -> Answer:
+        return self.answer_batch([question], params, None if scope is None else [scope])[0]
 
     # ------------------------------------------------------------------ pipelined
     @torch.inference_mode()
-    def _prepare(self, questions: list[str], stream, gate, params=None):
+    def _prepare(self, questions: list[str], stream, gate, params=None, scopes=None):
         """embed + kNN on a side HIP stream (held back by ``gate`` until the running
         generation is ``lead_steps`` from its end), then host-side prompt assembly and
         (``params`` given) the batch's KV-block reservation."""
@@ -256,14 +280,14 @@ class RAGPipeline:
                 evs[0].record(stream)
                 qemb = self.embed(questions)
                 evs[1].record(stream)
-                _, I = self.index.search(qemb, self.k)
+                _, I = self.search(qemb, scopes)
                 evs[2].record(stream)
                 I = self._host_ids(I)       # waits for this side stream only
             host = None
         else:
             qemb = self.embed(questions)
             tm = time.perf_counter()
-            _, I = self.index.search(qemb, self.k)
+            _, I = self.search(qemb, scopes)
             I = self._host_ids(I)
             host = (tm - t0, time.perf_counter() - tm)
         t1 = time.perf_counter()
@@ -282,7 +306,7 @@ class RAGPipeline:
 
     @torch.inference_mode()
     def answer_pipelined(self, batches: list[list[str]], params: SamplingParams | None = None,
-                         lead_steps: int | None = None):
+                         lead_steps: int | None = None, scopes: list | None = None):
         """Yield (answers, StageTimes, latency_s) per batch.  Batch i+1's embedding and
         kNN search run on a side HIP stream and its prompt assembly + KV reservation on a
         helper thread, released when batch i's decode is ``lead_steps`` steps from its
@@ -290,7 +314,8 @@ class RAGPipeline:
         (prefill + decode graphs queued behind batch i) before batch i is collected and
         detokenised on a second helper thread, so the GPU never waits on host work between
         batches.  Latency is measured on the GPU clock from the moment batch i+1's
-        embedding may start to its answers being ready."""
+        embedding may start to its answers being ready.  ``scopes``: per batch ``None`` or the
+        list of per-question scope requests (see :meth:`search`)."""
         import concurrent.futures as cf
 
         params = params or SamplingParams(stop_on_eos=True)
@@ -352,7 +377,8 @@ class RAGPipeline:
         # the batch, so collecting after launch() returned left the GPU idle meanwhile
         with cf.ThreadPoolExecutor(1, thread_name_prefix="rag-prep") as ex, \
                 cf.ThreadPoolExecutor(1, thread_name_prefix="rag-collect") as col:
-            fut = ex.submit(self._prepare, batches[0], stream, None, params) if batches else None
+            sc = (lambda i: scopes[i]) if scopes is not None else (lambda i: None)
+            fut = ex.submit(self._prepare, batches[0], stream, None, params, sc(0)) if batches else None
             fin = None
             try:
                 for i in range(len(batches)):
@@ -366,7 +392,9 @@ class RAGPipeline:
                     adapt()
                     nxt = batches[i + 1] if i + 1 < len(batches) else None
 
-                    def on_step(step, total, nxt=nxt):
+                    nxt_sc = sc(i + 1) if nxt is not None else None
+
+                    def on_step(step, total, nxt=nxt, nxt_sc=nxt_sc):
                         nonlocal fut, fin, pending
                         if pending is not None and fin is None:
                             p, pending = pending, None
@@ -376,7 +404,7 @@ class RAGPipeline:
                             if cuda:
                                 gate = torch.cuda.Event()
                                 gate.record()
-                            fut = ex.submit(self._prepare, nxt, stream, gate, params)
+                            fut = ex.submit(self._prepare, nxt, stream, gate, params, nxt_sc)
 
                     if reserved is None and pending is not None and len(prompts) <= eng.max_batch:
                         # no KV reservation (pool held by the batch in flight): collect that
@@ -390,7 +418,7 @@ class RAGPipeline:
                         h = None
                         outs = eng.generate(prompts, params, on_step=on_step)
                     if nxt is not None and fut is None:   # single-step generations
-                        fut = ex.submit(self._prepare, nxt, stream, None, params)
+                        fut = ex.submit(self._prepare, nxt, stream, None, params, nxt_sc)
                     if pending is not None:   # no decode step enqueued: collect batch i-1 now
                         p, pending = pending, None
                         fin = col.submit(finish, p)

@@ -16,6 +16,12 @@ from pydantic import BaseModel, Field
 # ---------------------------------------------------------------- llm-qa
 class Query(BaseModel):
     question: str
+    # optional retrieval scope: one patient's chunks (inside the window, if any) plus the
+    # knowledge base unless excluded; a request without them is served as before
+    patient_id: Optional[str] = None
+    from_date: Optional[str] = None
+    to_date: Optional[str] = None
+    include_knowledge_base: bool = True
 
 
 class AskResponse(BaseModel):
@@ -49,6 +55,10 @@ class SearchHit(BaseModel):
 class SearchRequest(BaseModel):
     query: str
     k: int = 3
+    patient_id: Optional[str] = None
+    from_date: Optional[str] = None
+    to_date: Optional[str] = None
+    include_knowledge_base: bool = True
 
 
 # ---------------------------------------------------------------- synthese-comparative

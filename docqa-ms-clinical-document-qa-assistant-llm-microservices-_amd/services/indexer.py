@@ -19,6 +19,8 @@ HTTP (the endpoint the reference's synthese-comparative expects but nobody serve
 synthese-comparative/core/retrieval_client.py:72-91):
   GET  /api/search/patient-snippets?patient_id&from_date&to_date&focus -> [{doc_id, text}]
   POST /api/search {"query", "k"} -> hits;  GET /api/index/stats;  GET /health
+    optional patient_id / from_date / to_date / include_knowledge_base scope the search to
+    one patient's chunks (inside the window) plus, unless excluded, the knowledge base
 """
 from __future__ import annotations
 
@@ -37,6 +39,7 @@ from ..config import Settings
 from ..index import faiss_io
 from ..index.flat import FlatIndex  # noqa: F401  (the default store type)
 from ..index.hybrid import load_index, make_index
+from ..index.scope import ScopeColumns, scope_request
 from ..pipeline.corpus import embed_records
 from ..schemas import SearchRequest
 from ..store import metadata_io
@@ -93,6 +96,8 @@ class SemanticIndexer:
         self.metadata: list[dict] = metadata if metadata is not None else []
         self.patients = PatientIndex()
         self.patients.rebuild(self.metadata)
+        self.scopes = ScopeColumns(device)     # row tags / days of the scoped search
+        self.scopes.rebuild(self.metadata)
         self.lock = threading.RLock()
         self.on_indexed = on_indexed  # callback(doc_id) e.g. docs DB status -> INDEXED
         self._ch = None
@@ -124,6 +129,7 @@ class SemanticIndexer:
                 self.index = load_index(self.st, self.index_path, self.device)
                 self.metadata = metadata_io.read_metadata(self.meta_path)
                 self.patients.rebuild(self.metadata)
+                self.scopes.rebuild(self.metadata)
                 if len(self.metadata) != self.index.ntotal:
                     raise RuntimeError(f"index/metadata mismatch: {self.index.ntotal} vs {len(self.metadata)}")
                 covered = read_snapshot_marker(self.marker_path)["wal_seq"]
@@ -132,6 +138,7 @@ class SemanticIndexer:
                 self.index = make_index(self.st, self.encoder.cfg.hidden, self.device)
                 self.metadata = []
                 self.patients.rebuild(self.metadata)
+                self.scopes.rebuild(self.metadata)
                 if build_if_missing:
                     recs = kb_records_from_dir(self.st.default_data_dir) or synthetic_kb_records()
                     self.add_records(recs, log=False)
@@ -142,6 +149,7 @@ class SemanticIndexer:
                     self.index.add(torch.from_numpy(vecs.copy()))
                     self.metadata.extend(recs)
                     self.patients.extend(self.metadata)
+                    self.scopes.extend(self.metadata)
                     replayed += len(recs)
                 if replayed:
                     logger.info("replayed %d vectors from the write-ahead log", replayed)
@@ -184,6 +192,7 @@ class SemanticIndexer:
             self.index.add(emb)
             self.metadata.extend(recs)
             self.patients.extend(self.metadata)
+            self.scopes.extend(self.metadata)
             self.version += 1
         return len(recs)
 
@@ -262,10 +271,15 @@ class SemanticIndexer:
 
     # ------------------------------------------------------------------ query
     @torch.inference_mode()
-    def search(self, query: str, k: int = 3) -> list[dict]:
+    def search(self, query: str, k: int = 3, scope: dict | None = None) -> list[dict]:
+        """``scope``: None, or a scope request (index/scope.py ``scope_request``) -- the hits
+        then come from that patient / window (and the knowledge base unless excluded) only."""
         q = self.encoder.encode(self.tok.encode_batch([query]))
         with self.lock:
-            D, I = self.index.search(q, k)
+            if scope is None:
+                D, I = self.index.search(q, k)
+            else:
+                D, I = self.index.search_scoped(q, k, self.scopes, self.scopes.scope_rows([scope]))
             dl, il = D[0].tolist(), I[0].tolist()
             # a sharded index: surface a failed cross-rank gather (stale peer rows) after the
             # host sync above instead of serving it (index/sharded.py check_gather)
@@ -323,7 +337,13 @@ def create_app(indexer: SemanticIndexer) -> FastAPI:
     def search(req: SearchRequest):
         if indexer.index is None:
             return JSONResponse(status_code=503, content={"detail": "Index non chargé."})
-        return indexer.search(req.query, req.k)
+        try:
+            scope = scope_request(req.patient_id, req.from_date, req.to_date, req.include_knowledge_base)
+        except ValueError as e:
+            return JSONResponse(status_code=422, content={"detail": str(e)})
+        if scope is None:
+            return indexer.search(req.query, req.k)
+        return indexer.search(req.query, req.k, scope)
 
     @app.get("/api/search/patient-snippets")
     def patient_snippets(patient_id: str, from_date: str | None = None, to_date: str | None = None,

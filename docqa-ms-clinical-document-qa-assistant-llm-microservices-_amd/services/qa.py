@@ -2,6 +2,10 @@
 
 Contract (llm-qa/main.py:108-126 and synthese-comparative/core/llm_client.py:42-54):
   POST /ask/                {"question"} -> {"answer", "sources": [source x k]}
+                            optional patient_id / from_date / to_date /
+                            include_knowledge_base scope the retrieval to one patient's
+                            chunks (inside the window) plus, unless excluded, the knowledge
+                            base (index/scope.py); 422 on an unparseable date
                             503 {"detail": "Index non chargé."} when no index is loaded
   POST /api/llm/summarize   {"prompt"}   -> {"summary"}   (expected by synthese, missing
                             in the reference; served here)
@@ -35,9 +39,22 @@ from fastapi.responses import JSONResponse, PlainTextResponse
 
 from ..config import Settings
 from ..engine.llm_engine import SamplingParams
+from ..index.scope import scope_request
 from ..schemas import AskResponse, Query, SummarizeRequest, SummarizeResponse
 from ..utils import tracing
 from ..utils.metrics import Metrics
+
+
+def ask_payload(question: str, scope: dict | None):
+    """The batcher payload of an ask: the plain question when it has no scope."""
+    return question if scope is None else {"question": question, "scope": scope}
+
+
+def _ask_parts(asks) -> tuple[list[str], list | None]:
+    """(questions, scopes) of queued asks; scopes is None when no ask carries one."""
+    qs = [it[1]["question"] if isinstance(it[1], dict) else it[1] for it in asks]
+    scopes = [it[1].get("scope") if isinstance(it[1], dict) else None for it in asks]
+    return qs, (scopes if any(s is not None for s in scopes) else None)
 
 
 def penalty_defaults(st: Settings) -> dict:
@@ -89,7 +106,9 @@ class DynamicBatcher:
         sums = [b for b in batch if b[0] == "summarize"]
         try:
             if asks:
-                res = self.pipe.answer_batch([b[1] for b in asks], self._params())
+                qs, scopes = _ask_parts(asks)
+                res = (self.pipe.answer_batch(qs, self._params()) if scopes is None
+                       else self.pipe.answer_batch(qs, self._params(), scopes=scopes))
                 for (_, _, f, t0), r in zip(asks, res):
                     self.metrics.observe("ask_latency_s", time.perf_counter() - t0)
                     f.set_result({"answer": r.answer, "sources": r.sources})
@@ -269,9 +288,9 @@ class ContinuousBatcher:
         sums = [it for it in items if it[0] == "summarize"]
         if asks:
             tp0 = time.perf_counter()
-            qs = [it[1] for it in asks]
+            qs, scopes = _ask_parts(asks)
             qemb = pipe.embed(qs)
-            _, I = pipe.index.search(qemb, pipe.k)
+            _, I = pipe.index.search(qemb, pipe.k) if scopes is None else pipe.search(qemb, scopes)
             I = pipe._host_ids(I)
             prompts = pipe.build_prompts(qs, I)
             te = time.perf_counter()
@@ -365,7 +384,12 @@ class ReplicaRouter:
         i = self._pick()
         try:
             if self.targets[i] is None:
-                return await asyncio.wrap_future(self.local.submit(kind, payload[key]))
+                local = payload[key]
+                if kind == "ask":      # remote replicas get the scope fields, the local batcher the scope
+                    local = ask_payload(local, scope_request(payload.get("patient_id"), payload.get("from_date"),
+                                                             payload.get("to_date"),
+                                                             payload.get("include_knowledge_base", True)))
+                return await asyncio.wrap_future(self.local.submit(kind, local))
             r = await self.client.post(self.targets[i] + path, json=payload)
             return JSONResponse(status_code=r.status_code, content=r.json())
         finally:
@@ -397,10 +421,18 @@ def create_app(pipeline=None, settings: Settings | None = None, lockstep=None,
     async def ask_question(query: Query):
         if not ready():
             return JSONResponse(status_code=503, content={"detail": "Index non chargé."})
+        try:
+            scope = scope_request(query.patient_id, query.from_date, query.to_date, query.include_knowledge_base)
+        except ValueError as e:
+            return JSONResponse(status_code=422, content={"detail": str(e)})
         metrics.inc("ask_requests")
         if router is not None:
-            return await router.call("ask", "/ask/", {"question": query.question}, "question")
-        fut = app.state.batcher.submit("ask", query.question)
+            payload = {"question": query.question}
+            if scope is not None:
+                payload.update(patient_id=query.patient_id, from_date=query.from_date, to_date=query.to_date,
+                               include_knowledge_base=query.include_knowledge_base)
+            return await router.call("ask", "/ask/", payload, "question")
+        fut = app.state.batcher.submit("ask", ask_payload(query.question, scope))
         return await asyncio.wrap_future(fut)
 
     @app.post("/api/llm/summarize", response_model=SummarizeResponse)
