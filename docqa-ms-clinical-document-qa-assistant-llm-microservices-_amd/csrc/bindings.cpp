@@ -5,6 +5,7 @@
 // the side streams the pipeline uses for embed/search/generate overlap.
 #include <torch/library.h>
 #include <algorithm>
+#include <climits>
 #include <tuple>
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -52,6 +53,7 @@ static void debug_sync(const char* name) {
 
 at::Tensor rmsnorm(const at::Tensor& x, const at::Tensor& w, double eps) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_CONTIG(x); CHECK_CONTIG(w);
+  CHECK_GPU(w); CHECK_ALIGN16(x); CHECK_ALIGN16(w);
   const int H = x.size(-1);
   TORCH_CHECK(w.numel() == H, "rmsnorm weight size mismatch");
   c10::DeviceGuard g(x.device());
@@ -63,9 +65,11 @@ at::Tensor rmsnorm(const at::Tensor& x, const at::Tensor& w, double eps) {
 
 at::Tensor add_rmsnorm(const at::Tensor& x, at::Tensor residual, const at::Tensor& w, double eps) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(residual); CHECK_BF16(w);
-  CHECK_CONTIG(x); CHECK_CONTIG(residual);
+  CHECK_CONTIG(x); CHECK_CONTIG(residual); CHECK_CONTIG(w);
+  CHECK_GPU(residual); CHECK_GPU(w); CHECK_ALIGN16(x); CHECK_ALIGN16(residual); CHECK_ALIGN16(w);
   TORCH_CHECK(x.sizes() == residual.sizes(), "add_rmsnorm shape mismatch");
   const int H = x.size(-1);
+  TORCH_CHECK(w.numel() == H, "add_rmsnorm weight size mismatch");
   c10::DeviceGuard g(x.device());
   auto out = at::empty_like(x);
   CHECK_RC(docqa_add_rmsnorm(x.data_ptr(), residual.data_ptr(), w.data_ptr(), out.data_ptr(),
@@ -76,10 +80,13 @@ at::Tensor add_rmsnorm(const at::Tensor& x, at::Tensor residual, const at::Tenso
 at::Tensor layernorm(const at::Tensor& x, const c10::optional<at::Tensor>& residual,
                      const at::Tensor& gamma, const at::Tensor& beta, double eps) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(gamma); CHECK_BF16(beta);
+  CHECK_GPU(gamma); CHECK_GPU(beta); CHECK_CONTIG(gamma); CHECK_CONTIG(beta);
+  CHECK_ALIGN16(x); CHECK_ALIGN16(gamma); CHECK_ALIGN16(beta);
   const int H = x.size(-1);
+  TORCH_CHECK(gamma.numel() == H && beta.numel() == H, "layernorm gamma / beta size mismatch");
   const void* rp = nullptr;
   if (residual.has_value()) {
-    CHECK_BF16(*residual); CHECK_CONTIG(*residual);
+    CHECK_GPU(*residual); CHECK_BF16(*residual); CHECK_CONTIG(*residual); CHECK_ALIGN16(*residual);
     TORCH_CHECK(residual->sizes() == x.sizes(), "layernorm residual shape mismatch");
     rp = residual->data_ptr();
   }
@@ -108,33 +115,64 @@ static bool kv_fp8(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t
   return true;
 }
 
+// positions / slot_mapping of a T-token rope_cache call, and its fp32 [max_pos, D] table
+static void check_rope_meta(const at::Tensor& positions, const c10::optional<at::Tensor>& slot_mapping,
+                            const at::Tensor& cos_sin, int64_t T, int64_t D) {
+  CHECK_GPU(positions); CHECK_I32(positions); CHECK_CONTIG(positions);
+  TORCH_CHECK(positions.numel() == T, "rope_cache: one position per token");
+  CHECK_GPU(cos_sin); CHECK_CONTIG(cos_sin); CHECK_ALIGN16(cos_sin);
+  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat, "cos_sin must be fp32");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == D, "cos_sin: [max_pos, D]");
+  if (slot_mapping.has_value()) {
+    CHECK_GPU(*slot_mapping); CHECK_I32(*slot_mapping); CHECK_CONTIG(*slot_mapping);
+    TORCH_CHECK(slot_mapping->numel() == T, "rope_cache: one slot per token");
+  }
+}
+
+// bf16 paged pools [num_blocks, Hkv, BS, D], written with 8- and 16-byte stores
+static void check_bf16_caches(const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t Hkv, int64_t D) {
+  CHECK_GPU(k_cache); CHECK_GPU(v_cache); CHECK_BF16(k_cache); CHECK_BF16(v_cache);
+  CHECK_CONTIG(k_cache); CHECK_CONTIG(v_cache); CHECK_ALIGN16(k_cache); CHECK_ALIGN16(v_cache);
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() && k_cache.size(1) == Hkv &&
+                  k_cache.size(3) == D && k_cache.size(2) >= 1, "KV cache: [num_blocks, Hkv, BS, D]");
+}
+
 void rope_cache(at::Tensor qkv, const at::Tensor& positions, const at::Tensor& cos_sin,
                 const c10::optional<at::Tensor>& slot_mapping, at::Tensor k_cache,
                 at::Tensor v_cache, int64_t Hq, int64_t Hkv, int64_t D) {
-  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_I32(positions);
-  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat, "cos_sin must be fp32");
-  TORCH_CHECK(qkv.stride(-1) == 1, "qkv rows must be contiguous");
-  TORCH_CHECK(qkv.size(-1) == (Hq + 2 * Hkv) * D, "qkv width mismatch");
+  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_ALIGN16(qkv);
+  TORCH_CHECK(qkv.dim() >= 1 && qkv.size(-1) == (Hq + 2 * Hkv) * D, "qkv width mismatch");
+  // rows of a 2-D qkv may sit in a wider buffer (a column slice): the kernel takes the row
+  // stride, which must keep every row 16-byte aligned; any other layout must be contiguous
+  int64_t row_stride = qkv.size(-1);
+  if (qkv.dim() == 2 && !qkv.is_contiguous()) {
+    TORCH_CHECK(qkv.stride(1) == 1 && qkv.stride(0) >= qkv.size(1) && qkv.stride(0) % 8 == 0,
+                "qkv: rows contiguous, row stride a multiple of 8 elements");
+    row_stride = qkv.stride(0);
+  } else {
+    CHECK_CONTIG(qkv);
+  }
+  TORCH_CHECK(row_stride <= INT_MAX, "qkv row stride out of range");
   const int T = qkv.numel() / qkv.size(-1);
+  check_rope_meta(positions, slot_mapping, cos_sin, T, D);
   const int* sm = nullptr;
   int BS = 1;
   if (slot_mapping.has_value()) {
-    CHECK_I32(*slot_mapping);
     sm = slot_mapping->data_ptr<int>();
     if (kv_fp8(k_cache, v_cache, Hkv, D)) {
-      CHECK_ALIGN16(qkv);
       c10::DeviceGuard g8(qkv.device());
       CHECK_RC(docqa_rope_cache8(qkv.data_ptr(), positions.data_ptr<int>(), cos_sin.data_ptr<float>(), sm,
-                                 k_cache.data_ptr(), v_cache.data_ptr(), T, Hq, Hkv, D, qkv.size(-1),
+                                 k_cache.data_ptr(), v_cache.data_ptr(), T, Hq, Hkv, D, (int)row_stride,
                                  k_cache.size(2), stream()), "rope_cache (fp8 cache)");
       return;
     }
+    check_bf16_caches(k_cache, v_cache, Hkv, D);
     BS = k_cache.size(2);  // [num_blocks, Hkv, BS, D]
   }
   c10::DeviceGuard g(qkv.device());
   CHECK_RC(docqa_rope_cache(qkv.data_ptr(), positions.data_ptr<int>(), cos_sin.data_ptr<float>(),
                             sm, sm ? k_cache.data_ptr() : nullptr, sm ? v_cache.data_ptr() : nullptr,
-                            T, Hq, Hkv, D, qkv.size(-1), BS, stream()), "rope_cache");
+                            T, Hq, Hkv, D, (int)row_stride, BS, stream()), "rope_cache");
 }
 
 // token-granular prefix copies: K/V rows [0, m) of block src -> block dst in every pool
@@ -172,6 +210,9 @@ at::Tensor add_rmsnorm_splitk(const at::Tensor& P, at::Tensor residual, const at
               "partials must be fp32 or bf16 [S, rows, H]");
   TORCH_CHECK(P.size(1) * P.size(2) == residual.numel() && P.size(2) == residual.size(-1),
               "add_rmsnorm_splitk shape mismatch");
+  CHECK_GPU(residual); CHECK_GPU(w); CHECK_CONTIG(w);
+  TORCH_CHECK(w.numel() == P.size(2), "add_rmsnorm_splitk weight size mismatch");
+  CHECK_ALIGN16(P); CHECK_ALIGN16(residual); CHECK_ALIGN16(w);
   c10::DeviceGuard g(P.device());
   auto out = at::empty_like(residual);
   if (P.scalar_type() == at::kBFloat16)
@@ -189,19 +230,19 @@ at::Tensor add_rmsnorm_splitk(const at::Tensor& P, at::Tensor residual, const at
 at::Tensor rope_cache_splitk(const at::Tensor& P, const at::Tensor& positions, const at::Tensor& cos_sin,
                              const c10::optional<at::Tensor>& slot_mapping, at::Tensor k_cache,
                              at::Tensor v_cache, int64_t Hq, int64_t Hkv, int64_t D) {
-  CHECK_GPU(P); CHECK_CONTIG(P); CHECK_I32(positions);
+  CHECK_GPU(P); CHECK_CONTIG(P); CHECK_ALIGN16(P);
   TORCH_CHECK((P.scalar_type() == at::kFloat || P.scalar_type() == at::kBFloat16) && P.dim() == 3,
               "partials must be fp32 or bf16 [S, T, width]");
-  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat, "cos_sin must be fp32");
   TORCH_CHECK(P.size(2) == (Hq + 2 * Hkv) * D, "qkv width mismatch");
   const int T = P.size(1);
+  check_rope_meta(positions, slot_mapping, cos_sin, T, D);
   const int* sm = nullptr;
   int BS = 1;
   bool f8 = false;
   if (slot_mapping.has_value()) {
-    CHECK_I32(*slot_mapping);
     sm = slot_mapping->data_ptr<int>();
     f8 = kv_fp8(k_cache, v_cache, Hkv, D);
+    if (!f8) check_bf16_caches(k_cache, v_cache, Hkv, D);
     BS = k_cache.size(2);
   }
   c10::DeviceGuard g(P.device());
@@ -244,7 +285,7 @@ at::Tensor silu_mul_splitk(const at::Tensor& P) {
 }
 
 at::Tensor silu_mul(const at::Tensor& gu, bool interleaved) {
-  CHECK_GPU(gu); CHECK_BF16(gu); CHECK_CONTIG(gu);
+  CHECK_GPU(gu); CHECK_BF16(gu); CHECK_CONTIG(gu); CHECK_ALIGN16(gu);
   const int I2 = gu.size(-1);
   auto sizes = gu.sizes().vec();
   sizes.back() = I2 / 2;
@@ -258,10 +299,15 @@ at::Tensor silu_mul(const at::Tensor& gu, bool interleaved) {
 at::Tensor bias_act(const at::Tensor& x, const at::Tensor& bias,
                     const c10::optional<at::Tensor>& residual, bool gelu) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_CONTIG(x); CHECK_BF16(bias);
+  CHECK_GPU(bias); CHECK_CONTIG(bias); CHECK_ALIGN16(x); CHECK_ALIGN16(bias);
   const int N = x.size(-1);
   TORCH_CHECK(bias.numel() == N, "bias size mismatch");
   const void* rp = nullptr;
-  if (residual.has_value()) { CHECK_BF16(*residual); CHECK_CONTIG(*residual); rp = residual->data_ptr(); }
+  if (residual.has_value()) {
+    CHECK_GPU(*residual); CHECK_BF16(*residual); CHECK_CONTIG(*residual); CHECK_ALIGN16(*residual);
+    TORCH_CHECK(residual->numel() == x.numel(), "bias_act residual size mismatch");
+    rp = residual->data_ptr();
+  }
   c10::DeviceGuard g(x.device());
   auto out = at::empty_like(x);
   CHECK_RC(docqa_bias_act(x.data_ptr(), bias.data_ptr(), rp, out.data_ptr(), x.numel() / N, N,
@@ -301,14 +347,28 @@ at::Tensor bert_embed_ln(const at::Tensor& ids, const at::Tensor& pos,
                          const at::Tensor& wpe, const at::Tensor& wtt, const at::Tensor& gamma,
                          const at::Tensor& beta, double eps) {
   CHECK_GPU(ids); CHECK_I32(ids); CHECK_I32(pos); CHECK_BF16(wte);
+  CHECK_GPU(pos); CHECK_GPU(wte); CHECK_GPU(wpe); CHECK_GPU(wtt); CHECK_GPU(gamma); CHECK_GPU(beta);
+  CHECK_BF16(wpe); CHECK_BF16(wtt); CHECK_BF16(gamma); CHECK_BF16(beta);
+  CHECK_CONTIG(ids); CHECK_CONTIG(pos); CHECK_CONTIG(wte); CHECK_CONTIG(wpe); CHECK_CONTIG(wtt);
+  CHECK_CONTIG(gamma); CHECK_CONTIG(beta);
+  TORCH_CHECK(wte.dim() == 2 && wpe.dim() == 2 && wtt.dim() == 2, "bert_embed_ln: tables are [rows, H]");
   const int H = wte.size(1);
+  TORCH_CHECK(wpe.size(1) == H && wtt.size(1) == H && gamma.numel() == H && beta.numel() == H,
+              "bert_embed_ln: wpe, wtt, gamma and beta must have H columns");
+  TORCH_CHECK(wte.size(0) >= 1 && wpe.size(0) >= 1 && wtt.size(0) >= 1, "bert_embed_ln: empty table");
+  TORCH_CHECK(pos.numel() == ids.numel(), "bert_embed_ln: one position per token");
   const int* tt = nullptr;
-  if (token_type.has_value()) { CHECK_I32(*token_type); tt = token_type->data_ptr<int>(); }
+  if (token_type.has_value()) {
+    CHECK_GPU(*token_type); CHECK_I32(*token_type); CHECK_CONTIG(*token_type);
+    TORCH_CHECK(token_type->numel() == ids.numel(), "bert_embed_ln: one token type per token");
+    tt = token_type->data_ptr<int>();
+  }
   c10::DeviceGuard g(ids.device());
   auto out = at::empty({ids.numel(), H}, wte.options());
   CHECK_RC(docqa_bert_embed_ln(ids.data_ptr<int>(), pos.data_ptr<int>(), tt, wte.data_ptr(),
                                wpe.data_ptr(), wtt.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                               out.data_ptr(), ids.numel(), H, (float)eps, stream()), "bert_embed_ln");
+                               out.data_ptr(), ids.numel(), H, (int)wte.size(0), (int)wpe.size(0),
+                               (int)wtt.size(0), (float)eps, stream()), "bert_embed_ln");
   return out;
 }
 
@@ -1887,6 +1947,8 @@ at::Tensor coarse_probes(const at::Tensor& xq, const at::Tensor& cent, const at:
 
 at::Tensor pool_l2(const at::Tensor& h, const at::Tensor& cu_seqlens, bool mean, bool normalize) {
   CHECK_GPU(h); CHECK_BF16(h); CHECK_CONTIG(h); CHECK_I32(cu_seqlens);
+  CHECK_GPU(cu_seqlens); CHECK_CONTIG(cu_seqlens); CHECK_ALIGN16(h);
+  TORCH_CHECK(cu_seqlens.numel() >= 1, "pool_l2: cu_seqlens of B + 1 entries");
   const int H = h.size(-1);
   const int B = cu_seqlens.numel() - 1;
   c10::DeviceGuard g(h.device());

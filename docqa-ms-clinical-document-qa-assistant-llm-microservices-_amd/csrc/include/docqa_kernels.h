@@ -58,7 +58,7 @@ int docqa_decode_advance(const int64_t* nxt, int64_t* out, int* tokens, int* pos
                          int* context_lens, const int* valid, int B, hipStream_t s);
 int docqa_bert_embed_ln(const int* ids, const int* pos, const int* tt, const void* wte,
                         const void* wpe, const void* wtt, const void* g, const void* b, void* out,
-                        int T, int H, float eps, hipStream_t s);
+                        int T, int H, int V, int NP, int NT, float eps, hipStream_t s);
 int docqa_argmax(const void* logits, int rows, int V, int ld, int is_bf16, float* ws_v, int* ws_i,
                  int splits, int64_t* out, hipStream_t s);
 int docqa_token_cls_argmax(const void* h, int ldh, const void* w, const void* bias, int n_rows,

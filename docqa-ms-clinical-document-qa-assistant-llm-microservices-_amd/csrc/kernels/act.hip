@@ -12,6 +12,15 @@
 using namespace docqa;
 
 __device__ __forceinline__ float silu(float x) { return x / (1.f + __expf(-x)); }
+// silu(x) * u.  Below x = -88.7 __expf(-x) overflows and x / inf is -0, while silu(x) * u is
+// still a (sub)normal bf16 value down to x ~ -97: there 1 + e^-x == e^-x in fp32, so
+// silu(x) = x * e^x, with e^x taken as two factors e^(x/2) so that no factor is an fp32
+// denormal.  Above -80 this is silu(x) * u bit for bit.
+__device__ __forceinline__ float silu_times(float x, float u) {
+  if (x >= -80.f) return silu(x) * u;
+  const float t = __expf(0.5f * x);
+  return x * t * u * t;
+}
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 // IL: gate|up rows interleaved in blocks of 8 (the layout the decode GEMM's fused SwiGLU
@@ -32,7 +41,7 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const uint16_t* __restric
     unpack8(row[IL ? 2 * c : c], g);
     unpack8(row[IL ? 2 * c + 1 : cpr + c], u);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = silu(g[j]) * u[j];
+    for (int j = 0; j < 8; ++j) o[j] = silu_times(g[j], u[j]);
     reinterpret_cast<uint4*>(out + t * (size_t)I)[c] = pack8(o);
   }
 }
@@ -64,7 +73,7 @@ __global__ __launch_bounds__(256) void silu_mul_splitk_kernel(const float* __res
     const float u[8] = {v[2].x, v[2].y, v[2].z, v[2].w, v[3].x, v[3].y, v[3].z, v[3].w};
     float o[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = silu(bf2f(f2bf(g[j]))) * bf2f(f2bf(u[j]));
+    for (int j = 0; j < 8; ++j) o[j] = silu_times(bf2f(f2bf(g[j])), bf2f(f2bf(u[j])));
     reinterpret_cast<uint4*>(out + (size_t)t * I)[c] = pack8(o);
   }
 }
@@ -114,7 +123,7 @@ __global__ __launch_bounds__(256) void silu_mul_splitk16_kernel(const uint16_t* 
     }
     float o[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = silu(bf2f(f2bf(g[j]))) * bf2f(f2bf(u[j]));
+    for (int j = 0; j < 8; ++j) o[j] = silu_times(bf2f(f2bf(g[j])), bf2f(f2bf(u[j])));
     reinterpret_cast<uint4*>(out + (size_t)t * I)[c] = pack8(o);
   }
 }

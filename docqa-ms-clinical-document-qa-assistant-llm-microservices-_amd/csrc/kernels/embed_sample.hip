@@ -80,14 +80,20 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(
     const int* __restrict__ ids, const int* __restrict__ pos, const int* __restrict__ tt,
     const uint16_t* __restrict__ wte, const uint16_t* __restrict__ wpe,
     const uint16_t* __restrict__ wtt, const uint16_t* __restrict__ gamma,
-    const uint16_t* __restrict__ beta, uint16_t* __restrict__ out, int T, int H, float eps) {
+    const uint16_t* __restrict__ beta, uint16_t* __restrict__ out, int T, int H, int V, int NP, int NT,
+    float eps) {
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (t >= T) return;
   const int nchunk = H >> 3;
-  const uint4* w = reinterpret_cast<const uint4*>(wte + (size_t)ids[t] * H);
-  const uint4* p = reinterpret_cast<const uint4*>(wpe + (size_t)pos[t] * H);
-  const uint4* y = reinterpret_cast<const uint4*>(wtt + (size_t)(tt ? tt[t] : 0) * H);
+  // out-of-range token / position / type indices read row 0, never past a table (as
+  // embedding_gather_kernel does)
+  const int id = (unsigned)ids[t] < (unsigned)V ? ids[t] : 0;
+  const int ps = (unsigned)pos[t] < (unsigned)NP ? pos[t] : 0;
+  const int ty = tt && (unsigned)tt[t] < (unsigned)NT ? tt[t] : 0;
+  const uint4* w = reinterpret_cast<const uint4*>(wte + (size_t)id * H);
+  const uint4* p = reinterpret_cast<const uint4*>(wpe + (size_t)ps * H);
+  const uint4* y = reinterpret_cast<const uint4*>(wtt + (size_t)ty * H);
   float v[NV][8];
   float s = 0.f;
 #pragma unroll
@@ -359,13 +365,13 @@ int docqa_embed_rmsnorm(const int* ids, const void* table, const void* w, void* 
 
 int docqa_bert_embed_ln(const int* ids, const int* pos, const int* tt, const void* wte,
                         const void* wpe, const void* wtt, const void* g, const void* b, void* out,
-                        int T, int H, float eps, hipStream_t s) {
+                        int T, int H, int V, int NP, int NT, float eps, hipStream_t s) {
   if (T == 0) return 0;
-  if (H % 8 != 0 || !docqa_aligned16(wte) || !docqa_aligned16(wpe) || !docqa_aligned16(wtt) ||
+  if (H % 8 != 0 || V < 1 || NP < 1 || NT < 1 || !docqa_aligned16(wte) || !docqa_aligned16(wpe) || !docqa_aligned16(wtt) ||
       !docqa_aligned16(g) || !docqa_aligned16(b) || !docqa_aligned16(out)) return -1;
   const int nv = (H / 8 + 63) / 64;
   dim3 grid((T + 3) / 4);
-#define BE(N) bert_embed_ln_kernel<N><<<grid, 256, 0, s>>>(ids, pos, tt, (const uint16_t*)wte, (const uint16_t*)wpe, (const uint16_t*)wtt, (const uint16_t*)g, (const uint16_t*)b, (uint16_t*)out, T, H, eps)
+#define BE(N) bert_embed_ln_kernel<N><<<grid, 256, 0, s>>>(ids, pos, tt, (const uint16_t*)wte, (const uint16_t*)wpe, (const uint16_t*)wtt, (const uint16_t*)g, (const uint16_t*)b, (uint16_t*)out, T, H, V, NP, NT, eps)
   if (nv <= 1) BE(1); else if (nv <= 2) BE(2); else if (nv <= 4) BE(4); else return -1;
 #undef BE
   DOCQA_CHECK_LAUNCH();

@@ -1332,7 +1332,8 @@ def embedding(ids, table):
 
 def bert_embed_ln(ids, pos, token_type, wte, wpe, wtt, gamma, beta, eps):
     if _gpu(wte):
-        return _native().bert_embed_ln(ids, pos, token_type, wte, wpe, wtt, gamma, beta, eps)
+        return _native().bert_embed_ln(ids.contiguous(), pos.contiguous(), token_type, wte, wpe, wtt, gamma, beta,
+                                       eps)
     return ref.bert_embed_ln(ids, pos, token_type, wte, wpe, wtt, gamma, beta, eps)
 
 

@@ -132,7 +132,10 @@ def silu_mul(gu, interleaved: bool = False):
         g, u = v[..., 0, :].flatten(-2), v[..., 1, :].flatten(-2)
     else:
         g, u = gu.float().chunk(2, dim=-1)
-    return (F.silu(g) * u).to(gu.dtype)
+    # below g = -88.7 exp(-g) overflows in fp32 and silu(g) becomes -0 although silu(g) * u is
+    # still a (sub)normal bf16 value: there silu(g) = g * e^g, with e^g as two e^(g/2) factors
+    t = torch.exp(0.5 * g)
+    return torch.where(g >= -80.0, F.silu(g) * u, g * t * u * t).to(gu.dtype)
 
 
 def glu_interleave(gate, up):
