@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace docqa {
 
@@ -44,6 +45,37 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   v.x = pack2(f[0], f[1]); v.y = pack2(f[2], f[3]);
   v.z = pack2(f[4], f[5]); v.w = pack2(f[6], f[7]);
   return v;
+}
+
+// silu(x) and silu(x) * u for the SwiGLU kernels (act.hip) and every fused SwiGLU GEMM epilogue,
+// so that the fused and the unfused gate|up paths give the same bits.
+__device__ __forceinline__ float silu(float x) { return x / (1.f + __expf(-x)); }
+// silu(x) * u.  Below x = -88.7 __expf(-x) overflows and x / inf is -0, while silu(x) * u is
+// still a (sub)normal bf16 value down to x ~ -97: there 1 + e^-x == e^-x in fp32, so
+// silu(x) = x * e^x, with e^x taken as two factors e^(x/2) so that no factor is an fp32
+// denormal.  Above -80 this is silu(x) * u bit for bit.
+__device__ __forceinline__ float silu_times(float x, float u) {
+  if (x >= -80.f) return silu(x) * u;
+  const float t = __expf(0.5f * x);
+  return x * t * u * t;
+}
+// The same in two passes, for GEMM epilogues with many (gate, up) pairs per lane, where the
+// second exp of silu_times (the compiler evaluates both sides and selects) would cost every
+// pair: the first pass stores silu(x) * u and keeps the smallest gate the lane has seen
+// (start lo at 0); where silu_second_pass says a lane of the wave met a gate below -80 -- in
+// a real model, never -- the wave repeats its pass with silu_times.
+__device__ __forceinline__ float silu_times_first(float x, float u, float& lo) {
+  lo = fminf(lo, x);
+  return silu(x) * u;
+}
+__device__ __forceinline__ bool silu_second_pass(float lo) {
+  return __builtin_amdgcn_ballot_w64(lo < -80.f) != 0;
+}
+// one pair in either pass (SECOND: std::true_type / std::false_type)
+template <class SECOND>
+__device__ __forceinline__ float silu_times_pass(float x, float u, float& lo, SECOND) {
+  if constexpr (SECOND::value) return silu_times(x, u);
+  else return silu_times_first(x, u, lo);
 }
 
 // 8 OCP e4m3 codes -> their bf16 values, packed like 8 bf16 in a uint4

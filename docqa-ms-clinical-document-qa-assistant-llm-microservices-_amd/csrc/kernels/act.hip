@@ -11,16 +11,6 @@
 
 using namespace docqa;
 
-__device__ __forceinline__ float silu(float x) { return x / (1.f + __expf(-x)); }
-// silu(x) * u.  Below x = -88.7 __expf(-x) overflows and x / inf is -0, while silu(x) * u is
-// still a (sub)normal bf16 value down to x ~ -97: there 1 + e^-x == e^-x in fp32, so
-// silu(x) = x * e^x, with e^x taken as two factors e^(x/2) so that no factor is an fp32
-// denormal.  Above -80 this is silu(x) * u bit for bit.
-__device__ __forceinline__ float silu_times(float x, float u) {
-  if (x >= -80.f) return silu(x) * u;
-  const float t = __expf(0.5f * x);
-  return x * t * u * t;
-}
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 
 // IL: gate|up rows interleaved in blocks of 8 (the layout the decode GEMM's fused SwiGLU

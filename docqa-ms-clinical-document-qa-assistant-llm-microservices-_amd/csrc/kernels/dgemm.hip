@@ -89,7 +89,6 @@ __device__ __forceinline__ int w_off(int row, int ch) {  // [rows][128] stage, 1
   return row * BKD + ((ch ^ (row & 15)) << 3);
 }
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
 
 // value of the lane 8 positions away inside each 16-lane row (DPP row_ror:8)
 __device__ __forceinline__ float row_swap8(float v) {
@@ -376,9 +375,10 @@ __global__ __launch_bounds__(256) void dgemm_kernel(const uint16_t* __restrict__
     else Y[(size_t)row * N + col] = f2bf(v);
   };
   // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns later
-  auto store_glu = [&](int row, int col, float g, float u) {
+  float glu_lo = 0.f;   // the smallest gate this lane has seen (silu_times_first)
+  auto store_glu = [&](int row, int col, float g, float u, auto second) {
     const float gb = bf2f(f2bf(g)), ub = bf2f(f2bf(u));   // as the unfused bf16 GEMM output
-    Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_f(gb) * ub);
+    Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_times_pass(gb, ub, glu_lo, second));
   };
   if constexpr (EPI == EPI_ARGMAX) {
     // LM head + greedy pick: the [rows, 64] logit tile through LDS (past the k-group
@@ -433,20 +433,26 @@ __global__ __launch_bounds__(256) void dgemm_kernel(const uint16_t* __restrict__
     return;
   }
   if constexpr (KW == 1) {
+    auto sweep = [&](auto second) {
 #pragma unroll
-    for (int mi = 0; mi < MPW; ++mi)
+      for (int mi = 0; mi < MPW; ++mi)
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
+        for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = (mt * MPW + mi) * 16 + fq * 4 + r, col = n0 + nt * 16 + fr;
-          if constexpr (EPI == EPI_GLU) {
-            const float u = row_swap8(acc[mi][nt][r]);
-            if (row < M && (fr & 8) == 0) store_glu(row, col, acc[mi][nt][r], u);
-          } else if (row < M) {
-            store(row, col, acc[mi][nt][r]);
+          for (int r = 0; r < 4; ++r) {
+            const int row = (mt * MPW + mi) * 16 + fq * 4 + r, col = n0 + nt * 16 + fr;
+            if constexpr (EPI == EPI_GLU) {
+              const float u = row_swap8(acc[mi][nt][r]);
+              if (row < M && (fr & 8) == 0) store_glu(row, col, acc[mi][nt][r], u, second);
+            } else if (row < M) {
+              store(row, col, acc[mi][nt][r]);
+            }
           }
-        }
+    };
+    sweep(std::false_type{});
+    if constexpr (EPI == EPI_GLU) {
+      if (silu_second_pass(glu_lo)) sweep(std::true_type{});   // a gate below -80: silu_times for the wave's pairs
+    }
   } else {
     // sum the KW k-groups through LDS (ring is free after the last barrier + wait)
     __syncthreads();
@@ -461,18 +467,24 @@ __global__ __launch_bounds__(256) void dgemm_kernel(const uint16_t* __restrict__
       for (int g = 0; g < KW; ++g) v += rf[(((g * MT + m) * NT + nt) * 64 + ln) * 4 + r];
       return v;
     };
+    auto sweep = [&](auto second) {
 #pragma unroll
-    for (int e = 0; e < MT * NT; ++e) {
-      const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
-      const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
-      const int nt = q % NT, m = q / NT;
-      const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
-      if (row >= M) continue;
-      if constexpr (EPI == EPI_GLU) {
-        if ((ln & 8) == 0) store_glu(row, col, sum_k(m, nt, ln, r), sum_k(m, nt, ln + 8, r));
-      } else {
-        store(row, col, sum_k(m, nt, ln, r));
+      for (int e = 0; e < MT * NT; ++e) {
+        const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
+        const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
+        const int nt = q % NT, m = q / NT;
+        const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
+        if (row >= M) continue;
+        if constexpr (EPI == EPI_GLU) {
+          if ((ln & 8) == 0) store_glu(row, col, sum_k(m, nt, ln, r), sum_k(m, nt, ln + 8, r), second);
+        } else {
+          store(row, col, sum_k(m, nt, ln, r));
+        }
       }
+    };
+    sweep(std::false_type{});
+    if constexpr (EPI == EPI_GLU) {
+      if (silu_second_pass(glu_lo)) sweep(std::true_type{});   // a gate below -80: silu_times for the wave's pairs
     }
   }
   if constexpr (NORM) {
@@ -820,7 +832,10 @@ __global__ __launch_bounds__(256) void gemv_kernel(const uint16_t* __restrict__ 
       const float g = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
       const float u = red[0][tid + 8] + red[1][tid + 8] + red[2][tid + 8] + red[3][tid + 8];
       const float gv = bf2f(f2bf(g)), uv = bf2f(f2bf(u));   // as the bf16 GEMM output
-      Y[(n0 >> 1) + tid] = f2bf(silu_f(gv) * uv);
+      Y[(n0 >> 1) + tid] = f2bf(silu(gv) * uv);
+      // a gate below -80 (never in a real model): the store repeated with silu_times, behind a
+      // branch of its own so that its second exp stays off every other workgroup's tail
+      if (silu_second_pass(gv)) Y[(n0 >> 1) + tid] = f2bf(silu_times(gv, uv));
     }
   }
 }
@@ -1063,7 +1078,10 @@ __global__ __launch_bounds__(256) void gemv8_kernel(const uint16_t* __restrict__
     const float g = __shfl(v, gi, 64), u = __shfl(v, gi + 8, 64);
     if (tid < R / 2) {
       const float gv = bf2f(f2bf(g)), uv = bf2f(f2bf(u));   // as the bf16 GEMM output
-      Y[(n0 >> 1) + tid] = f2bf(silu_f(gv) * uv);
+      Y[(n0 >> 1) + tid] = f2bf(silu(gv) * uv);
+      // a gate below -80 (never in a real model): the store repeated with silu_times, behind a
+      // branch of its own so that its second exp stays off every other workgroup's tail
+      if (silu_second_pass(gv)) Y[(n0 >> 1) + tid] = f2bf(silu_times(gv, uv));
     }
   }
 }
@@ -1291,7 +1309,10 @@ __global__ __launch_bounds__(256) void gemv4_kernel(const uint16_t* __restrict__
     const float g = __shfl(v, gi, 64), u = __shfl(v, gi + 8, 64);
     if (tid < R / 2) {
       const float gv = bf2f(f2bf(g)), uv = bf2f(f2bf(u));   // as the bf16 GEMM output
-      Y[(n0 >> 1) + tid] = f2bf(silu_f(gv) * uv);
+      Y[(n0 >> 1) + tid] = f2bf(silu(gv) * uv);
+      // a gate below -80 (never in a real model): the store repeated with silu_times, behind a
+      // branch of its own so that its second exp stays off every other workgroup's tail
+      if (silu_second_pass(gv)) Y[(n0 >> 1) + tid] = f2bf(silu_times(gv, uv));
     }
   }
 }
@@ -1593,23 +1614,30 @@ __global__ __launch_bounds__(256) void dgemm8_kernel(const uint16_t* __restrict_
     }
     return;
   }
+  float glu_lo = 0.f;   // EPI_GLU: the smallest gate this lane has seen (silu_times_first)
+  auto sweep = [&](auto second) {
 #pragma unroll
-  for (int e = 0; e < MT * NT; ++e) {
-    const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
-    const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
-    const int nt = q % NT, m = q / NT;
-    const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
-    if (row >= M) continue;
-    if constexpr (EPI == EPI_GLU) {
-      // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns later, both
-      // rounded to bf16 first, as the unfused bf16 GEMM output
-      if ((ln & 8) == 0) {
-        const float gb = bf2f(f2bf(sum_k(m, nt, ln, r))), ub = bf2f(f2bf(sum_k(m, nt, ln + 8, r)));
-        Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_f(gb) * ub);
+    for (int e = 0; e < MT * NT; ++e) {
+      const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
+      const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
+      const int nt = q % NT, m = q / NT;
+      const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
+      if (row >= M) continue;
+      if constexpr (EPI == EPI_GLU) {
+        // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns later, both
+        // rounded to bf16 first, as the unfused bf16 GEMM output
+        if ((ln & 8) == 0) {
+          const float gb = bf2f(f2bf(sum_k(m, nt, ln, r))), ub = bf2f(f2bf(sum_k(m, nt, ln + 8, r)));
+          Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_times_pass(gb, ub, glu_lo, second));
+        }
+      } else {
+        P[((size_t)slice * M + row) * N + col] = sum_k(m, nt, ln, r);
       }
-    } else {
-      P[((size_t)slice * M + row) * N + col] = sum_k(m, nt, ln, r);
     }
+  };
+  sweep(std::false_type{});
+  if constexpr (EPI == EPI_GLU) {
+    if (silu_second_pass(glu_lo)) sweep(std::true_type{});   // a gate below -80: silu_times for the wave's pairs
   }
 }
 
@@ -1889,26 +1917,33 @@ __global__ __launch_bounds__(256) void dgemm8w_kernel(const uint16_t* __restrict
     }
     return;
   }
+  float glu_lo = 0.f;   // EPI_GLU: the smallest gate this lane has seen (silu_times_first)
+  auto sweep = [&](auto second) {
 #pragma unroll
-  for (int mi = 0; mi < MT; ++mi)
+    for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-    for (int j = 0; j < NPW; ++j)
+      for (int j = 0; j < NPW; ++j)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = mi * 16 + fq * 4 + r, col = n0 + (wave * NPW + j) * 16 + fr;
-        const float v = acc[mi][j][r] * sc[j];
-        if constexpr (EPI == EPI_GLU) {
-          // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns (lanes) later,
-          // both rounded to bf16 first, as the unfused bf16 GEMM output
-          const float u = row_swap8(v);
-          if (row < M && (fr & 8) == 0) {
-            const float gb = bf2f(f2bf(v)), ub = bf2f(f2bf(u));
-            Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_f(gb) * ub);
+        for (int r = 0; r < 4; ++r) {
+          const int row = mi * 16 + fq * 4 + r, col = n0 + (wave * NPW + j) * 16 + fr;
+          const float v = acc[mi][j][r] * sc[j];
+          if constexpr (EPI == EPI_GLU) {
+            // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns (lanes) later,
+            // both rounded to bf16 first, as the unfused bf16 GEMM output
+            const float u = row_swap8(v);
+            if (row < M && (fr & 8) == 0) {
+              const float gb = bf2f(f2bf(v)), ub = bf2f(f2bf(u));
+              Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_times_pass(gb, ub, glu_lo, second));
+            }
+          } else if (row < M) {
+            P[((size_t)slice * M + row) * N + col] = v;
           }
-        } else if (row < M) {
-          P[((size_t)slice * M + row) * N + col] = v;
         }
-      }
+  };
+  sweep(std::false_type{});
+  if constexpr (EPI == EPI_GLU) {
+    if (silu_second_pass(glu_lo)) sweep(std::true_type{});   // a gate below -80: silu_times for the wave's pairs
+  }
 }
 
 constexpr int MR8W_LO = MR8 + 1, MR8W_HI = 128;   // rows of the wide FP8 kernel
@@ -2225,23 +2260,30 @@ __global__ __launch_bounds__(256) void dgemm4_kernel(const uint16_t* __restrict_
     }
     return;
   }
+  float glu_lo = 0.f;   // EPI_GLU: the smallest gate this lane has seen (silu_times_first)
+  auto sweep = [&](auto second) {
 #pragma unroll
-  for (int e = 0; e < MT * NT; ++e) {
-    const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
-    const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
-    const int nt = q % NT, m = q / NT;
-    const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
-    if (row >= M) continue;
-    if constexpr (EPI == EPI_GLU) {
-      // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns later, both
-      // rounded to bf16 first, as the unfused bf16 GEMM output
-      if ((ln & 8) == 0) {
-        const float gb = bf2f(f2bf(sum_k(m, nt, ln, r))), ub = bf2f(f2bf(sum_k(m, nt, ln + 8, r)));
-        Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_f(gb) * ub);
+    for (int e = 0; e < MT * NT; ++e) {
+      const int idx = e * 256 + tid;                 // (m-tile, nt, lane, r)
+      const int r = idx & 3, ln = (idx >> 2) & 63, q = idx >> 8;
+      const int nt = q % NT, m = q / NT;
+      const int row = m * 16 + (ln >> 4) * 4 + r, col = n0 + nt * 16 + (ln & 15);
+      if (row >= M) continue;
+      if constexpr (EPI == EPI_GLU) {
+        // SwiGLU pair: gate value at an 8-block's low half, up value 8 columns later, both
+        // rounded to bf16 first, as the unfused bf16 GEMM output
+        if ((ln & 8) == 0) {
+          const float gb = bf2f(f2bf(sum_k(m, nt, ln, r))), ub = bf2f(f2bf(sum_k(m, nt, ln + 8, r)));
+          Y[(size_t)row * (N >> 1) + ((col >> 4) << 3) + (col & 7)] = f2bf(silu_times_pass(gb, ub, glu_lo, second));
+        }
+      } else {
+        P[((size_t)slice * M + row) * N + col] = sum_k(m, nt, ln, r);
       }
-    } else {
-      P[((size_t)slice * M + row) * N + col] = sum_k(m, nt, ln, r);
     }
+  };
+  sweep(std::false_type{});
+  if constexpr (EPI == EPI_GLU) {
+    if (silu_second_pass(glu_lo)) sweep(std::true_type{});   // a gate below -80: silu_times for the wave's pairs
   }
 }
 

@@ -126,20 +126,25 @@ __global__ __launch_bounds__(256) void gemm_kernel(const uint16_t* __restrict__ 
     // [16 p, 16 p + 8) are gate, [16 p + 8, 16 p + 16) up; C is [M, N / 2] =
     // silu(gate) * up, each input rounded to bf16 first (as the unfused bf16 GEMM output
     // would be).  Lane -> (row, pair p of the wave's 4)
-    for (int it = 0; it < 4; ++it) {
-      const int rloc = it * 16 + (lane >> 2), p = lane & 3;
-      const int gr = row0 + wr * 64 + rloc;
-      if (gr < M) {
-        float o[8];
+    float lo = 0.f;
+    auto sweep = [&](auto second) {
+      for (int it = 0; it < 4; ++it) {
+        const int rloc = it * 16 + (lane >> 2), p = lane & 3;
+        const int gr = row0 + wr * 64 + rloc;
+        if (gr < M) {
+          float o[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float g = bf2f(f2bf(st[rloc * 65 + p * 16 + e]));
-          const float u = bf2f(f2bf(st[rloc * 65 + p * 16 + 8 + e]));
-          o[e] = g / (1.f + __expf(-g)) * u;
+          for (int e = 0; e < 8; ++e) {
+            const float g = bf2f(f2bf(st[rloc * 65 + p * 16 + e]));
+            const float u = bf2f(f2bf(st[rloc * 65 + p * 16 + 8 + e]));
+            o[e] = silu_times_pass(g, u, lo, second);
+          }
+          *reinterpret_cast<uint4*>(C + (size_t)gr * (N >> 1) + ((col0 + wc * 64) >> 1) + p * 8) = pack8(o);
         }
-        *reinterpret_cast<uint4*>(C + (size_t)gr * (N >> 1) + ((col0 + wc * 64) >> 1) + p * 8) = pack8(o);
       }
-    }
+    };
+    sweep(std::false_type{});
+    if (silu_second_pass(lo)) sweep(std::true_type{});   // a gate below -80: silu_times for the wave's rows
     return;
   }
   // each wave writes its own 64 rows x 64 cols: lane -> (row group, 8-col chunk)

@@ -53,9 +53,6 @@ __device__ __forceinline__ int swz(int row, int ch) {
   else return row * 32 + ((ch ^ ((row >> 2) & 3)) << 3);
 }
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
-
-
 __device__ __forceinline__ void better(float& bv, int& bi, float v, int i) {
   if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
 }
@@ -94,36 +91,43 @@ __device__ __forceinline__ void mgemm_epilogue(f32x4 (&acc)[BM / WM / 16][BN / W
     constexpr int EPC = EPI == EPI_PARTIAL ? 4 : (EPI == EPI_BF16 || EPI == EPI_PARTIAL16) ? 8 : 16;
     constexpr int LPR = CW / EPC, RPS = 64 / LPR;          // lanes per row, rows per sweep
     if constexpr (EPI != EPI_ARGMAX) {
+      float lo = 0.f;   // EPI_GLU: the smallest gate this lane has seen (silu_times_first)
+      auto sweep = [&](auto second) {
 #pragma unroll
-      for (int it = 0; it < 16 / RPS; ++it) {
-        const int r = it * RPS + lane / LPR, c = (lane % LPR) * EPC;
-        float v[EPC];
+        for (int it = 0; it < 16 / RPS; ++it) {
+          const int r = it * RPS + lane / LPR, c = (lane % LPR) * EPC;
+          float v[EPC];
 #pragma unroll
-        for (int e = 0; e < EPC / 4; ++e) {
-          const float4 t = *reinterpret_cast<const float4*>(scr + r * SCR + c + e * 4);
-          v[e * 4] = t.x; v[e * 4 + 1] = t.y; v[e * 4 + 2] = t.z; v[e * 4 + 3] = t.w;
-        }
-        const int row = rbase + i * 16 + r, col = cbase + c;
-        if (row < M) {
-          if constexpr (EPI == EPI_PARTIAL) {
-            float* dst = P + ((size_t)slice * M + row) * N + col;
-            *reinterpret_cast<float4*>(dst) = float4{v[0], v[1], v[2], v[3]};
-          } else if constexpr (EPI == EPI_BF16) {
-            *reinterpret_cast<uint4*>(Y + (size_t)row * N + col) = pack8(v);
-          } else if constexpr (EPI == EPI_PARTIAL16) {
-            *reinterpret_cast<uint4*>(Y + ((size_t)slice * M + row) * N + col) = pack8(v);
-          } else {
-            // 16 consecutive columns = one (gate 8, up 8) interleave group
-            float o[8];
+          for (int e = 0; e < EPC / 4; ++e) {
+            const float4 t = *reinterpret_cast<const float4*>(scr + r * SCR + c + e * 4);
+            v[e * 4] = t.x; v[e * 4 + 1] = t.y; v[e * 4 + 2] = t.z; v[e * 4 + 3] = t.w;
+          }
+          const int row = rbase + i * 16 + r, col = cbase + c;
+          if (row < M) {
+            if constexpr (EPI == EPI_PARTIAL) {
+              float* dst = P + ((size_t)slice * M + row) * N + col;
+              *reinterpret_cast<float4*>(dst) = float4{v[0], v[1], v[2], v[3]};
+            } else if constexpr (EPI == EPI_BF16) {
+              *reinterpret_cast<uint4*>(Y + (size_t)row * N + col) = pack8(v);
+            } else if constexpr (EPI == EPI_PARTIAL16) {
+              *reinterpret_cast<uint4*>(Y + ((size_t)slice * M + row) * N + col) = pack8(v);
+            } else {
+              // 16 consecutive columns = one (gate 8, up 8) interleave group
+              float o[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float gv = bf2f(f2bf(v[e])), uv = bf2f(f2bf(v[8 + e]));   // as the bf16 GEMM output
-              o[e] = silu_f(gv) * uv;
+              for (int e = 0; e < 8; ++e) {
+                const float gv = bf2f(f2bf(v[e])), uv = bf2f(f2bf(v[8 + e]));   // as the bf16 GEMM output
+                o[e] = silu_times_pass(gv, uv, lo, second);
+              }
+              uint16_t* dst = Y + (size_t)row * (N >> 1) + (col >> 1);
+              *reinterpret_cast<uint4*>(dst) = pack8(o);
             }
-            uint16_t* dst = Y + (size_t)row * (N >> 1) + (col >> 1);
-            *reinterpret_cast<uint4*>(dst) = pack8(o);
           }
         }
+      };
+      sweep(std::false_type{});
+      if constexpr (EPI == EPI_GLU) {
+        if (silu_second_pass(lo)) sweep(std::true_type{});   // a gate below -80: silu_times for these 16 rows
       }
     } else {
       // 4 lanes per row, CW/4 columns each; the row's best (value, id) after 2 shuffles

@@ -84,7 +84,6 @@ __device__ __forceinline__ void glds_pair(const void* sbase, uint32_t v0, uint32
       : "memory");
 }
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.f + __expf(-x)); }
 
 // K range [kbeg, kbeg + 128 nit) of the 256 x 256 output tile at (m0, n0) into acc (zeroed
 // here), nit >= 1.  Returns with the wave rows re-aligned and every LDS buffer drained, so
@@ -292,23 +291,29 @@ __device__ __forceinline__ void pgemm_store(char* smem, f32x4 (&acc)[2][4][2][2]
   } else {
     // 16 consecutive GEMM columns = one (gate 8 | up 8) group: lane fr < 8 holds gate[fr],
     // lane fr + 8 the matching up (DPP row rotate by 8 pairs them); 32 outputs per wave row
+    float lo = 0.f;
+    auto sweep = [&](auto second) {
 #pragma unroll
-    for (int mh = 0; mh < 2; ++mh)
+      for (int mh = 0; mh < 2; ++mh)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int nh = 0; nh < 2; ++nh)
+          for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const float v = acc[mh][i][nh][j][r];
-              const float u = row_ror<8>(v);
-              if (fr < 8) {
-                const float gv = bf2f(f2bf(v)), uv = bf2f(f2bf(u));   // as the bf16 GEMM output
-                scr[(mh * 64 + i * 16 + fk * 4 + r) * SCR_PITCH + nh * 16 + j * 8 + fr] = f2bf(silu_f(gv) * uv);
+              for (int r = 0; r < 4; ++r) {
+                const float v = acc[mh][i][nh][j][r];
+                const float u = row_ror<8>(v);
+                if (fr < 8) {
+                  const float gv = bf2f(f2bf(v)), uv = bf2f(f2bf(u));   // as the bf16 GEMM output
+                  scr[(mh * 64 + i * 16 + fk * 4 + r) * SCR_PITCH + nh * 16 + j * 8 + fr] =
+                      f2bf(silu_times_pass(gv, uv, lo, second));
+                }
               }
-            }
+    };
+    sweep(std::false_type{});
+    if (silu_second_pass(lo)) sweep(std::true_type{});   // a gate below -80: silu_times for the wave's tile
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     // 32 outputs (64 B) per row: 4 lanes per row, 16 rows per sweep
 #pragma unroll 4
