@@ -92,6 +92,11 @@ class Settings:
     # read by engine/llm_engine.py LLMEngine(kv_dtype=None))
     kv_cache: str = field(default_factory=lambda: os.getenv("DOCQA_KV_CACHE", "bf16"))
     top_k: int = field(default_factory=lambda: env_int("TOP_K", 3))
+    # retrieval mode of requests that carry no search_mode: dense | lexical | hybrid
+    # (pipeline/rag.py SEARCH_MODES); LEXICAL_INDEX=1 builds the BM25 term columns at start-up
+    # instead of on the first lexical / hybrid request (index/lexical.py)
+    retrieval_mode: str = field(default_factory=lambda: os.getenv("RETRIEVAL_MODE", "dense"))
+    lexical_index: bool = field(default_factory=lambda: env_bool("LEXICAL_INDEX", "false"))
     max_new_tokens: int = field(default_factory=lambda: env_int("MAX_NEW_TOKENS", 256))
     temperature: float = field(default_factory=lambda: float(os.getenv("TEMPERATURE", "0")))
     # llama.cpp-style penalties over the last REPEAT_LAST_N tokens of prompt + output (neutral

@@ -1911,6 +1911,88 @@ std::tuple<at::Tensor, at::Tensor> knn_scoped(const at::Tensor& xb, const at::Te
   return {out_d, out_i};
 }
 
+// BM25 scan over CSR term columns with the top-k fused (lexical.hip): row_ptr int64 [N+1]
+// (entries of row r: row_ptr[r] .. row_ptr[r+1], all < terms.numel()), terms int32 [E], tfs
+// uint8 [E], dl int32 [N], qterms int32 / qweights fp32 [nq, 32]; tags / days / scope as knn_scoped
+std::tuple<at::Tensor, at::Tensor> bm25_topk(const at::Tensor& row_ptr, const at::Tensor& terms,
+                                             const at::Tensor& tfs, const at::Tensor& dl,
+                                             const at::Tensor& qterms, const at::Tensor& qweights, int64_t k,
+                                             double avgdl, double k1, double b,
+                                             const c10::optional<at::Tensor>& tags,
+                                             const c10::optional<at::Tensor>& days,
+                                             const c10::optional<at::Tensor>& scope, int64_t id_offset) {
+  CHECK_GPU(row_ptr); CHECK_GPU(terms); CHECK_GPU(tfs); CHECK_GPU(dl); CHECK_GPU(qterms); CHECK_GPU(qweights);
+  CHECK_CONTIG(row_ptr); CHECK_CONTIG(terms); CHECK_CONTIG(tfs); CHECK_CONTIG(dl); CHECK_CONTIG(qterms);
+  CHECK_CONTIG(qweights);
+  TORCH_CHECK(row_ptr.scalar_type() == at::kLong && row_ptr.dim() == 1 && row_ptr.numel() >= 1,
+              "bm25_topk: row_ptr must be int64 [N+1]");
+  const int64_t N64 = row_ptr.numel() - 1;
+  // 512 rows of head room: the kernel's tile and row indices stay in int
+  TORCH_CHECK(N64 < (int64_t(1) << 31) - 512 && terms.numel() < (int64_t(1) << 31),
+              "bm25_topk: N must be < 2^31 - 512 and E < 2^31");
+  const int N = (int)N64;
+  TORCH_CHECK(terms.scalar_type() == at::kInt && tfs.scalar_type() == at::kByte && terms.numel() == tfs.numel(),
+              "bm25_topk: terms int32 [E], tfs uint8 [E]");
+  TORCH_CHECK(dl.scalar_type() == at::kInt && dl.numel() == N, "bm25_topk: dl must be int32 [N]");
+  TORCH_CHECK(qterms.scalar_type() == at::kInt && qweights.scalar_type() == at::kFloat && qterms.dim() == 2 &&
+              qterms.size(1) == 32 && qweights.dim() == 2 && qweights.size(0) == qterms.size(0) &&
+              qweights.size(1) == 32, "bm25_topk: qterms int32 / qweights fp32 [nq, 32]");
+  TORCH_CHECK(k >= 1 && docqa_knn_kpad(k) > 0, "k must be in [1, 64]");
+  TORCH_CHECK(avgdl > 0, "bm25_topk: avgdl must be positive");
+  const int nq = qterms.size(0);
+  const bool scoped = scope.has_value();
+  const int *tp = nullptr, *dp = nullptr, *sp = nullptr;
+  if (scoped) {
+    TORCH_CHECK(tags.has_value() && days.has_value(), "bm25_topk: a scope needs tags and days");
+    const at::Tensor &tg = *tags, &dy = *days, &sc = *scope;
+    CHECK_GPU(tg); CHECK_GPU(dy); CHECK_GPU(sc); CHECK_CONTIG(tg); CHECK_CONTIG(dy); CHECK_CONTIG(sc);
+    TORCH_CHECK(tg.scalar_type() == at::kInt && dy.scalar_type() == at::kInt && tg.numel() == N && dy.numel() == N,
+                "bm25_topk: tags / days must be int32 [N]");
+    TORCH_CHECK(sc.scalar_type() == at::kInt && sc.dim() == 2 && sc.size(0) == nq && sc.size(1) == 4,
+                "bm25_topk: scope must be int32 [nq, 4]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(sc.data_ptr()) % 16 == 0, "bm25_topk: scope must be 16-byte aligned");
+    tp = tg.data_ptr<int>(); dp = dy.data_ptr<int>(); sp = sc.data_ptr<int>();
+  }
+  c10::DeviceGuard g(row_ptr.device());
+  auto out_s = at::empty({nq, k}, qweights.options());
+  auto out_i = at::empty({nq, k}, qweights.options().dtype(at::kLong));
+  if (N == 0 || nq == 0) {
+    out_s.fill_(-3.4028234663852886e38);
+    out_i.fill_(-1);
+    return {out_s, out_i};
+  }
+  const int nblk = docqa_bm25_workspace_blocks(N);
+  const int kp = docqa_knn_kpad(k);
+  auto ws_d = at::empty({nq, nblk, kp}, qweights.options());
+  auto ws_i = at::empty({nq, nblk, kp}, qweights.options().dtype(at::kInt));
+  CHECK_RC(docqa_bm25_topk(row_ptr.data_ptr<int64_t>(), terms.data_ptr<int>(), tfs.data_ptr<uint8_t>(),
+                           dl.data_ptr<int>(), N, qterms.data_ptr<int>(), qweights.data_ptr<float>(), nq, (int)k,
+                           (float)k1, (float)b, (float)(1.0 - b), (float)avgdl, tp, dp, sp, ws_d.data_ptr<float>(),
+                           ws_i.data_ptr<int>(), nblk, out_s.data_ptr<float>(), out_i.data_ptr<int64_t>(),
+                           id_offset, stream()), "bm25_topk");
+  return {out_s, out_i};
+}
+
+// per query: the first k of either list, or their reciprocal rank fusion (lexical.hip)
+std::tuple<at::Tensor, at::Tensor> rank_fuse(const at::Tensor& i_dense, const at::Tensor& i_lex,
+                                             const at::Tensor& mode, int64_t k, int64_t c) {
+  CHECK_GPU(i_dense); CHECK_GPU(i_lex); CHECK_GPU(mode); CHECK_CONTIG(i_dense); CHECK_CONTIG(i_lex);
+  CHECK_CONTIG(mode); CHECK_I32(mode);
+  TORCH_CHECK(i_dense.scalar_type() == at::kLong && i_lex.scalar_type() == at::kLong && i_dense.dim() == 2 &&
+              i_lex.dim() == 2 && i_dense.size(0) == i_lex.size(0) && mode.numel() == i_dense.size(0),
+              "rank_fuse: I_dense / I_lex int64 [nq, <= 64], mode int32 [nq]");
+  TORCH_CHECK(i_dense.size(1) <= 64 && i_lex.size(1) <= 64 && k >= 1 && c >= 0 && c <= 100000,
+              "rank_fuse: lists of at most 64 ids, k >= 1, c in [0, 100000]");
+  const int nq = i_dense.size(0);
+  c10::DeviceGuard g(i_dense.device());
+  auto out_f = at::empty({nq, k}, i_dense.options().dtype(at::kFloat));
+  auto out_i = at::empty({nq, k}, i_dense.options());
+  CHECK_RC(docqa_rank_fuse(i_dense.data_ptr<int64_t>(), (int)i_dense.size(1), i_lex.data_ptr<int64_t>(),
+                           (int)i_lex.size(1), mode.data_ptr<int>(), nq, (int)k, (int)c, out_f.data_ptr<float>(),
+                           out_i.data_ptr<int64_t>(), stream()), "rank_fuse");
+  return {out_f, out_i};
+}
+
 // IVF coarse quantizer, wide probes: int64 [nq, nprobe] nearest centroids (ascending, ties
 // to the lower id) for nprobe <= 512
 // exact fp32 x @ w^T on the coarse quantizer's MFMA tiles (the IVF-PQ query pre-rotation)
@@ -2179,6 +2261,10 @@ TORCH_LIBRARY(docqa, m) {
   m.def("knn_scoped(Tensor xb, Tensor xb_norms, Tensor tags, Tensor days, Tensor xq, Tensor scope, int k, "
         "bool inner_product, int id_offset) -> (Tensor, Tensor)");
   m.def("pool_l2(Tensor h, Tensor cu_seqlens, bool mean, bool normalize) -> Tensor");
+  m.def("bm25_topk(Tensor row_ptr, Tensor terms, Tensor tfs, Tensor dl, Tensor qterms, Tensor qweights, int k, "
+        "float avgdl, float k1, float b, Tensor? tags, Tensor? days, Tensor? scope, int id_offset) "
+        "-> (Tensor, Tensor)");
+  m.def("rank_fuse(Tensor i_dense, Tensor i_lex, Tensor mode, int k, int c) -> (Tensor, Tensor)");
   m.def("coarse_probes(Tensor xq, Tensor cent, Tensor cnorm, int nprobe) -> Tensor");
   m.def("fp32_gemm_nt(Tensor x, Tensor w) -> Tensor");
   m.def("ivfpq_search(Tensor xq, Tensor centroids, Tensor pq, Tensor codes, Tensor ids, "
@@ -2297,6 +2383,8 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("flash_prefill", &flash_prefill);
   m.impl("knn", &knn);
   m.impl("knn_scoped", &knn_scoped);
+  m.impl("bm25_topk", &bm25_topk);
+  m.impl("rank_fuse", &rank_fuse);
   m.impl("pool_l2", &pool_l2);
   m.impl("ivfpq_search", &ivfpq_search);
   m.impl("ivfpq_search_pt", &ivfpq_search_pt);

@@ -302,6 +302,17 @@ int docqa_knn_scoped(const void* xb, const float* norms, const int* tags, const 
                      int d, int is_bf16, const float* xq, const int* scope, int nq, int k,
                      int metric_ip, float* ws_d, int* ws_i, int nblk, float* out_d, int64_t* out_i,
                      int64_t id_offset, hipStream_t s);
+// BM25 scan over CSR term columns + fused top-k (lexical.hip); ws_d / ws_i [nq,
+// docqa_bm25_workspace_blocks(N), docqa_knn_kpad(k)]; tags / days / scope null: unscoped
+int docqa_bm25_workspace_blocks(int N);
+int docqa_bm25_topk(const int64_t* row_ptr, const int* terms, const uint8_t* tfs, const int* dl, int N,
+                    const int* qterms, const float* qweights, int nq, int k, float k1, float b,
+                    float one_minus_b, float avgdl, const int* tags, const int* days, const int* scope,
+                    float* ws_d, int* ws_i, int nblk, float* out_s, int64_t* out_i, int64_t id_offset,
+                    hipStream_t s);
+// per query: first k of either ranked id list (mode 0 / 1) or their reciprocal rank fusion (2)
+int docqa_rank_fuse(const int64_t* i_dense, int ld, const int64_t* i_lex, int ll, const int* mode, int nq,
+                    int k, int c, float* out_f, int64_t* out_i, hipStream_t s);
 
 int docqa_ivfpq_search(const float* xq, const float* centroids, const float* pq,
                        const uint8_t* codes, const int64_t* ids, const int64_t* list_off,

@@ -30,6 +30,7 @@
 // the epilogue fetches the bit of (query, row) from the row's lane, so the predicate is
 // evaluated once per pair.  Everything scoped is under `if constexpr (SCOPED)`.
 #include "docqa_common.h"
+#include "docqa_scope.h"
 #include "docqa_topk.h"
 #include <float.h>
 
@@ -37,14 +38,7 @@ using namespace docqa;
 
 namespace {
 
-// The scope predicate (the fp32 reference ops/reference.py knn_scoped states the same):
-//   row_tag == alt_tag || ((tag < 0 || row_tag == tag) && day_lo <= row_day && row_day <= day_hi)
-// s = (tag, alt_tag, day_lo, day_hi).  tag -1 = any tag; alt_tag -1 = none (row tags are
-// >= 0), 0 = also the knowledge base, exempt from the window; (INT32_MIN, INT32_MAX) = no
-// window; an undated row carries day INT32_MIN, so any real bound excludes it.
-__device__ __forceinline__ bool scope_match(const int4 s, int row_tag, int row_day) {
-  return row_tag == s.y || ((s.x < 0 || row_tag == s.x) && s.z <= row_day && row_day <= s.w);
-}
+// scope_match (docqa_scope.h): the scope predicate, shared with the lexical scan
 
 template <int K, bool IP, bool BF16, bool SCOPED>
 __global__ __launch_bounds__(256) void knn_tile_kernel(

@@ -139,6 +139,32 @@ class FlatIndex:
             return ops.knn_scoped(xb[:n], nm[:n], tags[:n], days[:n], xq, scope, k, self.metric == "ip",
                                   id_offset)
 
+    def search_lexical(self, cols, qterms, qweights, avgdl: float, k: int, scope_cols=None, scope=None,
+                       id_offset: int = 0):
+        """BM25 top-k over the rows' :class:`~docqa_amd.index.lexical.LexicalColumns`
+        (``qterms``, ``qweights``, ``avgdl``: its ``query_rows``); ``scope_cols`` + ``scope``
+        restrict every query as in :meth:`search_scoped`.  -> (S descending, I), -1 past the
+        matching rows.  Exact (the columns do not depend on the vectors); covers rows
+        ``[0, min(ntotal, cols.n[, scope_cols.n]))``."""
+        with self._lock:
+            n = min(self.ntotal, cols.n)      # before the buffers: they only ever grow
+            if scope is not None:
+                n = min(n, scope_cols.n)
+            bufs = [cols._row_ptr, cols._terms, cols._tfs, cols._dl]
+            tags = days = None
+            if scope is not None:
+                scope = torch.as_tensor(scope).to(self.device, dtype=torch.int32)
+                tags, days = scope_cols._tags, scope_cols._days
+                bufs += [tags, days]
+                tags, days = tags[:n], days[:n]
+            if self.device.type == "cuda":
+                # as in search(): the kernel may run on a side stream while these are dropped
+                s = torch.cuda.current_stream(self.device)
+                for t in bufs:
+                    t.record_stream(s)
+            return ops.bm25_topk(bufs[0][: n + 1], bufs[1], bufs[2], bufs[3][:n], qterms, qweights, k, avgdl,
+                                 tags=tags, days=days, scope=scope, id_offset=id_offset)
+
     def reconstruct(self, i: int) -> np.ndarray:
         return self._xb[i].float().cpu().numpy()
 

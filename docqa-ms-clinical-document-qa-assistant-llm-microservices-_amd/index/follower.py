@@ -25,6 +25,7 @@ from ..store import metadata_io
 from ..store.segment_log import read_snapshot_marker, tail_frames
 from . import faiss_io
 from .flat import FlatIndex
+from .lexical import LexicalColumns
 from .scope import ScopeColumns
 
 log = logging.getLogger("docqa.index.follower")
@@ -46,6 +47,13 @@ class IndexFollower:
             self.index = FlatIndex(d, "l2", device)
         self.metadata: list[dict] = []
         self.scopes = ScopeColumns(device)   # row tags / days of the scoped search
+        # term columns of the lexical / hybrid search: built by the first such request
+        # (ensure_lexical, the QA prep thread) or at start with LEXICAL_INDEX=1, then kept in
+        # step by the poll thread -- the lock keeps the two apart
+        self.lexical: LexicalColumns | None = None
+        self._lex_lock = threading.Lock()
+        self._device = device
+        self._lexical_at_start = bool(getattr(settings, "lexical_index", False))
         self.poll_s = poll_s
         self.last_seq = 0          # highest WAL sequence applied
         self._marker = None        # snapshot marker the current state is based on
@@ -78,7 +86,10 @@ class IndexFollower:
         xb = torch.from_numpy(data.xb) if n else torch.empty(0, self.index.d)
 
         def swap_meta():
-            self.metadata[:] = meta
+            with self._lex_lock:     # ensure_lexical() never reads a half-swapped list
+                self.metadata[:] = meta
+                if self.lexical is not None:
+                    self.lexical.rebuild(self.metadata)
             self.scopes.rebuild(self.metadata)
 
         if ivf is not None and hasattr(self.index, "ivf"):
@@ -107,6 +118,9 @@ class IndexFollower:
                 continue
             self.metadata.extend(recs)       # records first: every searchable id resolves
             self.scopes.extend(self.metadata)
+            with self._lex_lock:
+                if self.lexical is not None:
+                    self.lexical.extend(self.metadata)
             self.index.add(torch.from_numpy(vecs.copy()))
             self.last_seq = seq
             added += len(recs)
@@ -114,9 +128,20 @@ class IndexFollower:
             self.version += 1
         return added
 
+    def ensure_lexical(self) -> LexicalColumns:
+        """The BM25 term columns of the metadata list, built on the first call."""
+        with self._lex_lock:
+            if self.lexical is None:
+                cols = LexicalColumns(self._device)
+                cols.rebuild(self.metadata)
+                self.lexical = cols
+            return self.lexical
+
     # ------------------------------------------------------------------ background
     def start(self) -> "IndexFollower":
         self.poll()
+        if self._lexical_at_start:
+            self.ensure_lexical()
         if self._thread is None:
             self._thread = threading.Thread(target=self._run, name="index-follower", daemon=True)
             self._thread.start()

@@ -124,6 +124,14 @@ class IVFPQRefineIndex:
         with self._lock:
             return self.flat.search_scoped(xq, k, cols, scope, id_offset=id_offset)
 
+    def search_lexical(self, cols, qterms, qweights, avgdl: float, k: int, scope_cols=None, scope=None,
+                       id_offset: int = 0):
+        """The lexical scan is exact, trained or not: the term columns do not depend on the
+        vectors."""
+        with self._lock:
+            return self.flat.search_lexical(cols, qterms, qweights, avgdl, k, scope_cols=scope_cols, scope=scope,
+                                            id_offset=id_offset)
+
     def reconstruct(self, i: int) -> np.ndarray:
         return self.flat.reconstruct(i)
 

@@ -218,6 +218,12 @@ class ShardedIndex:
             "Tags would have to agree across ranks, and no service builds a sharded index. "
             "That belongs with sharding the deployed index.")
 
+    def search_lexical(self, cols, qterms, qweights, avgdl: float, k: int, scope_cols=None, scope=None,
+                       id_offset: int = 0):
+        raise NotImplementedError(
+            "Document frequencies and the average length would have to agree across ranks, and "
+            "no service builds a sharded index. That belongs with sharding the deployed index.")
+
     def _search(self, xq: torch.Tensor, k: int, **kw):
         nq = xq.shape[0]
         dev = xq.device

@@ -1938,6 +1938,45 @@ def knn_scoped(xb, xb_norms, tags, days, xq, scope, k: int, inner_product: bool 
     return ref.knn_scoped(xb, xb_norms, tags, days, xq, scope, k, inner_product, id_offset)
 
 
+def bm25_topk(row_ptr, terms, tfs, dl, qterms, qweights, k: int, avgdl: float, k1: float = 1.2, b: float = 0.75,
+              tags=None, days=None, scope=None, id_offset: int = 0):
+    """BM25 top-k over CSR term columns (index/lexical.py): -> (S fp32 [nq, k] descending, ties
+    towards the lower row, I int64 [nq, k]; -FLT_MAX / -1 past the matching rows); see
+    ``reference.bm25_topk`` for the arithmetic.  ``tags``, ``days`` and ``scope`` together
+    scope every query as in :func:`knn_scoped`.  GPU: the fused scan of
+    csrc/kernels/lexical.hip.  Outside its envelope (k > 64, query rows not 32 slots wide,
+    2^31 - 512 rows or 2^31 entries, a ``tfs`` that is not uint8, ``qweights`` not shaped like
+    ``qterms``) and with ``DOCQA_BM25=0`` (kill switch) the fp32 reference runs on the same
+    device instead of failing."""
+    scoped = tags is not None and days is not None and scope is not None
+    if not scoped:
+        tags = days = scope = None
+    if _gpu(row_ptr) and os.environ.get("DOCQA_BM25", "1") != "0":
+        if (1 <= k <= 64 and qterms.dim() == 2 and qterms.shape[1] == 32 and qweights.shape == qterms.shape
+                and tfs.dtype == torch.uint8 and tfs.numel() == terms.numel() and avgdl > 0
+                and row_ptr.numel() - 1 < (1 << 31) - 512 and terms.numel() < (1 << 31)):
+            i32 = lambda t: None if t is None else t.int().contiguous()  # noqa: E731
+            return _native().bm25_topk(row_ptr.long().contiguous(), terms.int().contiguous(), tfs.contiguous(),
+                                       dl.int().contiguous(), qterms.int().contiguous(),
+                                       qweights.float().contiguous(), k, float(avgdl), float(k1), float(b),
+                                       i32(tags), i32(days), i32(scope), id_offset)
+    return ref.bm25_topk(row_ptr, terms, tfs, dl, qterms, qweights, k, avgdl, k1, b, tags, days, scope, id_offset)
+
+
+def rank_fuse(I_dense, I_lex, mode, k: int, c: int = 60):
+    """Per query, by ``mode`` int32 [nq]: 0 the first k ids of ``I_dense``, 1 of ``I_lex``, 2
+    their reciprocal rank fusion (score = sum of 1 / (c + rank), compared exactly, ties towards
+    the lower id); lists of up to 64 ranked ids, negative entries ignored.  -> (F fp32 [nq, k],
+    I int64 [nq, k]), 0 / -1 in missing slots.  GPU: one wave per query (lexical.hip), no
+    host sync, so a mixed batch is a dense, a lexical and a fuse launch back to back."""
+    if _gpu(I_dense):
+        if I_dense.shape[1] > 64 or I_lex.shape[1] > 64 or not 0 <= c <= 100000:
+            raise ValueError("rank_fuse: lists of at most 64 ids and c in [0, 100000]")
+        return _native().rank_fuse(I_dense.long().contiguous(), I_lex.long().contiguous(),
+                                   mode.int().contiguous(), k, c)
+    return ref.rank_fuse(I_dense, I_lex, mode, k, c)
+
+
 def fp32_matmul_nt(x, w):
     """Exact fp32 ``x @ w.T`` on the coarse quantizer's MFMA tiles (coarse.hip) -- the IVF-PQ
     query pre-rotation on the GPU without a library GEMM; torch on the CPU."""

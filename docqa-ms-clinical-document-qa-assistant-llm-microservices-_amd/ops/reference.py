@@ -529,6 +529,103 @@ def knn_scoped(xb, xb_norms, tags, days, xq, scope, k, inner_product, id_offset)
     return D, I
 
 
+def bm25_topk(row_ptr, terms, tfs, dl, qterms, qweights, k, avgdl, k1=1.2, b=0.75, tags=None, days=None,
+              scope=None, id_offset=0):
+    """BM25 (Lucene >= 8: no ``(k1 + 1)`` factor) over CSR term columns, fp32 throughout:
+
+        K_r   = k1 * ((1 - b) + (b * dl_r) / avgdl)
+        s_q,r = sum over the row's entries, in entry order, of  w_q,t * (tf / (tf + K_r))
+
+    row_ptr int64 [N+1], terms int32 [E] (32-bit hashes, unique per row), tfs uint8 [E], dl
+    int32 [N]; qterms int32 / qweights fp32 [nq, 32], ``0xFFFFFFFF`` pads and a term repeated in
+    one query row counts once (its first slot).  A row competes iff it holds one of the
+    query's terms and passes its scope row (``knn_scoped``'s predicate; ``scope`` None:
+    unscoped).  -> (S fp32 [nq, k] descending, ties towards the lower row, I int64 [nq, k]);
+    missing slots hold ``-FLT_MAX`` / -1.  The sum order is the kernel's (csrc/kernels/lexical.hip)."""
+    dev = row_ptr.device
+    N, nq = row_ptr.numel() - 1, qterms.shape[0]
+    S = torch.full((nq, k), -3.4028234663852886e38, dtype=torch.float32, device=dev)
+    I = torch.full((nq, k), -1, dtype=torch.long, device=dev)
+    if N <= 0 or nq == 0:
+        return S, I
+    rp = row_ptr.long()
+    E = int(rp[-1])
+    row_of = torch.repeat_interleave(torch.arange(N, device=dev), rp[1:] - rp[:-1])
+    t = terms[:E].long() & 0xFFFFFFFF
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)  # noqa: E731 - every scalar rounded once
+    Kr = f32(k1) * (f32(1.0 - b) + (f32(b) * dl.float()) / f32(avgdl))
+    tf = tfs[:E].float()
+    x = tf / (tf + Kr[row_of])
+    match = None
+    if scope is not None:
+        rt, rd = tags.reshape(-1)[None, :].int(), days.reshape(-1)[None, :].int()
+        tag, alt, lo, hi = (scope.int()[:, j:j + 1] for j in range(4))
+        match = (rt == alt) | (((tag < 0) | (rt == tag)) & (lo <= rd) & (rd <= hi))
+    qt_host = (qterms.long() & 0xFFFFFFFF).tolist()
+    for q in range(nq):
+        first: dict[int, int] = {}
+        for j, h in enumerate(qt_host[q]):
+            if h != 0xFFFFFFFF and h not in first:
+                first[h] = j
+        if not first or E == 0:
+            continue
+        st = torch.tensor(sorted(first), dtype=torch.long, device=dev)
+        sw = qweights[q].float()[torch.tensor([first[h] for h in sorted(first)], dtype=torch.long, device=dev)]
+        pos = torch.searchsorted(st, t).clamp(max=st.numel() - 1)
+        he = (st[pos] == t).nonzero().squeeze(1)            # hit entries, ascending
+        if he.numel() == 0:
+            continue
+        c = sw[pos[he]] * x[he]
+        r = row_of[he]
+        idx = torch.arange(he.numel(), device=dev)
+        new = torch.ones_like(r, dtype=torch.bool)
+        new[1:] = r[1:] != r[:-1]
+        level = idx - torch.cummax(torch.where(new, idx, torch.zeros_like(idx)), 0).values
+        score = torch.zeros(N, dtype=torch.float32, device=dev)
+        for lv in range(int(level.max()) + 1):              # the lv-th hit of every row: one add per row
+            m = level == lv
+            score[r[m]] = score[r[m]] + c[m]
+        cand = torch.zeros(N, dtype=torch.bool, device=dev)
+        cand[r] = True
+        if match is not None:
+            cand &= match[q]
+        vals, order = torch.sort(score.masked_fill(~cand, -math.inf), descending=True, stable=True)
+        vals, order = vals[:k], order[:k]
+        ok = cand[order]
+        S[q, : vals.numel()] = torch.where(ok, vals, torch.full_like(vals, -3.4028234663852886e38))
+        I[q, : order.numel()] = torch.where(ok, order + id_offset, torch.full_like(order, -1))
+    return S, I
+
+
+def rank_fuse(I_dense, I_lex, mode, k, c=60):
+    """Per query (mode 0 / 1 / 2): the first k ids of ``I_dense``, of ``I_lex``, or of their
+    reciprocal rank fusion -- an id scores the sum over the lists holding it of
+    ``1 / (c + rank)``, rank = its 1-based position; negative ids are ignored and a repeated
+    id counts at its first position.  Order: score descending, compared exactly
+    (``fractions.Fraction``), ties towards the lower id.  -> (F fp32 [nq, k] = num / den of the
+    score, I int64 [nq, k]); missing slots hold 0 / -1."""
+    from fractions import Fraction
+
+    dev = I_dense.device
+    a_all, b_all, modes = I_dense.tolist(), I_lex.tolist(), mode.tolist()
+    nq = len(modes)
+    num = torch.zeros((nq, k), dtype=torch.float32)
+    den = torch.ones((nq, k), dtype=torch.float32)
+    I = torch.full((nq, k), -1, dtype=torch.long)
+    for q in range(nq):
+        score: dict[int, Fraction] = {}
+        for use, ids in ((modes[q] != 1, a_all[q]), (modes[q] != 0, b_all[q])):
+            seen = set()
+            for pos, i in enumerate(ids if use else ()):
+                if i >= 0 and i not in seen:
+                    seen.add(i)
+                    score[i] = score.get(i, Fraction(0)) + Fraction(1, c + pos + 1)
+        for j, (i, s) in enumerate(sorted(score.items(), key=lambda kv: (-kv[1], kv[0]))[:k]):
+            # the kernel's (num, den) are unreduced: (a + b, a b) or (1, a); both are exact in fp32
+            num[q, j], den[q, j], I[q, j] = s.numerator, s.denominator, i
+    return (num / den).to(dev), I.to(dev)
+
+
 def pool_l2(h, cu_seqlens, mean, normalize):
     cu = cu_seqlens.tolist()
     out = torch.zeros(len(cu) - 1, h.shape[-1], dtype=torch.float32, device=h.device)

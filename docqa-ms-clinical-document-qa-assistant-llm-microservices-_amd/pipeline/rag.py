@@ -24,6 +24,7 @@ import torch
 # over the decode step time
 _LEAD_MARGIN = float(os.environ.get("DOCQA_PIPELINE_LEAD_MARGIN", "1.5"))
 
+from .. import ops
 from ..utils import tracing
 from ..engine.llm_engine import LLMEngine, SamplingParams
 from ..prompts import CACHE_FRIENDLY_QA_TEMPLATE, REFERENCE_QA_TEMPLATE, qa_template
@@ -31,6 +32,10 @@ from ..prompts import CACHE_FRIENDLY_QA_TEMPLATE, REFERENCE_QA_TEMPLATE, qa_temp
 # QA prompt: the verbatim reference QA_CHAIN_PROMPT (llm-qa/main.py:71-93) by default, the
 # cache-friendly reordering with QA_TEMPLATE=cache_friendly (docqa_amd/prompts.py)
 DEFAULT_TEMPLATE = REFERENCE_QA_TEMPLATE
+
+# retrieval modes of a question, in ops.rank_fuse's numbering: the dense kNN hits, the BM25
+# hits, or their reciprocal rank fusion
+SEARCH_MODES = ("dense", "lexical", "hybrid")
 
 
 @dataclass
@@ -94,6 +99,12 @@ class RAGPipeline:
         # indexer's when one owns the (index, metadata) pair, else built lazily from metadata
         self.scopes = None
         self._own_scopes = None
+        # term columns of the lexical / hybrid search (index/lexical.py), built on the first
+        # such request: the owner's (``lexical_owner.ensure_lexical()``) when one keeps the
+        # (index, metadata) pair, else built from metadata here
+        self.lexical = None
+        self.lexical_owner = None
+        self._own_lexical = None
         # token ids of every retrieved chunk, tokenised once: a prompt is then assembled
         # from cached pieces split at paragraph boundaries (the byte-level BPE never merges
         # across a newline pre-token), so only the question is tokenised per request
@@ -122,31 +133,92 @@ class RAGPipeline:
             check()
         return ids
 
-    def search(self, qemb: torch.Tensor, scopes: list | None = None):
-        """(D, I) of the embedded questions' top-k.  ``scopes``: per question ``None`` or a
-        scope request (index/scope.py: patient_id, from_date, to_date,
-        include_knowledge_base); a batch without any takes the unscoped search, a mixed
-        batch is one scoped launch (``None`` = the any-scope row)."""
-        if scopes is None or all(s is None for s in scopes):
-            return self.index.search(qemb, self.k)
-        if len(scopes) != qemb.shape[0]:
-            raise ValueError("one scope per question")
+    def _scope_cols(self, device):
         if self.scopes is None:
             from ..index.scope import ScopeColumns
 
-            self._own_scopes = self.scopes = ScopeColumns(getattr(self.index, "device", qemb.device))
+            self._own_scopes = self.scopes = ScopeColumns(getattr(self.index, "device", device))
         if self._own_scopes is self.scopes:     # no follower / indexer keeps it in step
             if self.scopes.n > len(self.metadata):
                 self.scopes.rebuild(self.metadata)
             self.scopes.extend(self.metadata)
-        return self.index.search_scoped(qemb, self.k, self.scopes, self.scopes.scope_rows(scopes))
+        return self.scopes
 
-    def retrieve(self, questions: list[str], scopes: list | None = None):
+    def _lexical_cols(self, device):
+        """The term columns, built on the first lexical / hybrid request: the (index, metadata)
+        owner's (``lexical_owner.ensure_lexical()``, kept in step by it from then on), else
+        this pipeline's own, extended from the metadata list on every such request."""
+        if self.lexical is None:
+            if self.lexical_owner is not None:
+                self.lexical = self.lexical_owner.ensure_lexical()
+            else:
+                from ..index.lexical import LexicalColumns
+
+                self._own_lexical = self.lexical = LexicalColumns(getattr(self.index, "device", device))
+        if self._own_lexical is self.lexical:
+            if self.lexical.n > len(self.metadata):
+                self.lexical.rebuild(self.metadata)
+            self.lexical.extend(self.metadata)
+        return self.lexical
+
+    def search(self, qemb: torch.Tensor, scopes: list | None = None, modes: list | None = None,
+               texts: list | None = None):
+        """(D, I) of the embedded questions' top-k.  ``scopes``: per question ``None`` or a
+        scope request (index/scope.py: patient_id, from_date, to_date,
+        include_knowledge_base); a batch without any takes the unscoped search, a mixed
+        batch is one scoped launch (``None`` = the any-scope row).  ``modes``: per question
+        ``"dense"``, ``"lexical"`` or ``"hybrid"`` (``texts``: the questions, needed by the last
+        two); ``None`` or all dense is the dense search alone."""
+        if modes is not None and any(m != "dense" for m in modes):
+            return self._search_modes(qemb, scopes, modes, texts)
+        if scopes is None or all(s is None for s in scopes):
+            return self.index.search(qemb, self.k)
+        if len(scopes) != qemb.shape[0]:
+            raise ValueError("one scope per question")
+        cols = self._scope_cols(qemb.device)
+        return self.index.search_scoped(qemb, self.k, cols, cols.scope_rows(scopes))
+
+    def _search_modes(self, qemb, scopes, modes, texts):
+        """A batch with a lexical or hybrid question: the dense leg and the BM25 leg for the
+        whole batch at depth ``HYBRID_FETCH_K`` (default min(64, max(16, 4 k))), then
+        ``ops.rank_fuse`` picks per question the dense hits, the lexical hits or their
+        reciprocal rank fusion -- three launches, no host sync between them.  D is the
+        leg's own score: L2 distance, BM25 score or RRF value."""
+        nq, k = qemb.shape[0], self.k
+        if texts is None or len(texts) != nq or len(modes) != nq:
+            raise ValueError("one mode and one question text per question")
+        bad = [m for m in modes if m not in SEARCH_MODES]
+        if bad:
+            raise ValueError(f"search mode must be one of {SEARCH_MODES}, got {bad[0]!r}")
+        if k > 64:
+            raise ValueError("lexical / hybrid search serves k <= 64")
+        from ..index.lexical import fetch_depth
+
+        depth = fetch_depth(k)
+        lex = self._lexical_cols(qemb.device)
+        scoped = scopes is not None and any(s is not None for s in scopes)
+        if scoped and len(scopes) != nq:
+            raise ValueError("one scope per question")
+        cols = rows = None
+        if scoped:
+            cols = self._scope_cols(qemb.device)
+            rows = cols.scope_rows(scopes)
+            Dd, Id = self.index.search_scoped(qemb, depth, cols, rows)
+        else:
+            Dd, Id = self.index.search(qemb, depth)
+        qt, qw, avgdl = lex.query_rows(list(texts))
+        Sl, Il = self.index.search_lexical(lex, qt, qw, avgdl, depth, scope_cols=cols, scope=rows)
+        mode = torch.tensor([SEARCH_MODES.index(m) for m in modes], dtype=torch.int32).to(Id.device)
+        F, I = ops.rank_fuse(Id, Il, mode, k)
+        m = mode[:, None]
+        return torch.where(m == 0, Dd[:, :k], torch.where(m == 1, Sl[:, :k], F)), I
+
+    def retrieve(self, questions: list[str], scopes: list | None = None, modes: list | None = None):
         """(D, I) of the questions' top-k.  On a sharded index the hits are checked for a
         failed cross-rank gather here (one host sync on the search's ids) so no caller can
         use stale peer rows unchecked."""
         q = self.embed(questions)
-        D, I = self.search(q, scopes)
+        D, I = self.search(q, scopes, modes, questions)
         if getattr(self.index, "check_gather", None) is not None:
             self._host_ids(I)
         return D, I
@@ -231,7 +303,7 @@ class RAGPipeline:
 
     @torch.inference_mode()
     def answer_batch(self, questions: list[str], params: SamplingParams | None = None,
-                     scopes: list | None = None) -> list[Answer]:
+                     scopes: list | None = None, modes: list | None = None) -> list[Answer]:
         params = params or SamplingParams(stop_on_eos=True)
         t = StageTimes()
         t0 = time.perf_counter()
@@ -240,7 +312,7 @@ class RAGPipeline:
             self._sync()
         t1 = time.perf_counter()
         with tracing.span("rag.search", n=len(questions), k=self.k):
-            D, I = self.search(qemb, scopes)
+            D, I = self.search(qemb, scopes, modes, questions)
             I = self._host_ids(I)  # host needs ids to assemble the prompts
         t2 = time.perf_counter()
         with tracing.span("rag.prompt", n=len(questions)):
@@ -258,8 +330,10 @@ class RAGPipeline:
                               chunk_ids=list(ids)))
         return res
 
-    def answer(self, question: str, params: SamplingParams | None = None, scope: dict | None = None) -> Answer:
-        return self.answer_batch([question], params, None if scope is None else [scope])[0]
+    def answer(self, question: str, params: SamplingParams | None = None, scope: dict | None = None,
+               mode: str | None = None) -> Answer:
+        return self.answer_batch([question], params, None if scope is None else [scope],
+                                 None if mode is None else [mode])[0]
 
     # ------------------------------------------------------------------ pipelined
     @torch.inference_mode()

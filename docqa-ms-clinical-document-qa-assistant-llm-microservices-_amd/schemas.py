@@ -8,9 +8,13 @@ doc-ingestor/models.py:5-12 (document row), AMQP messages.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import List, Literal, Optional
 
 from pydantic import BaseModel, Field
+
+# retrieval mode of a question: the dense kNN hits, the BM25 hits or their reciprocal rank
+# fusion; None = the service default (RETRIEVAL_MODE).  Any other value is a 422.
+SearchMode = Optional[Literal["dense", "lexical", "hybrid"]]
 
 
 # ---------------------------------------------------------------- llm-qa
@@ -22,6 +26,10 @@ class Query(BaseModel):
     from_date: Optional[str] = None
     to_date: Optional[str] = None
     include_knowledge_base: bool = True
+    search_mode: SearchMode = None
+
+
+AskRequest = Query      # the reference's name for the /ask/ body is Query
 
 
 class AskResponse(BaseModel):
@@ -59,6 +67,7 @@ class SearchRequest(BaseModel):
     from_date: Optional[str] = None
     to_date: Optional[str] = None
     include_knowledge_base: bool = True
+    search_mode: SearchMode = None
 
 
 # ---------------------------------------------------------------- synthese-comparative

@@ -19,6 +19,8 @@ HTTP (the endpoint the reference's synthese-comparative expects but nobody serve
 synthese-comparative/core/retrieval_client.py:72-91):
   GET  /api/search/patient-snippets?patient_id&from_date&to_date&focus -> [{doc_id, text}]
   POST /api/search {"query", "k"} -> hits;  GET /api/index/stats;  GET /health
+    optional search_mode dense | lexical | hybrid (default RETRIEVAL_MODE): kNN, BM25 or their
+    reciprocal rank fusion; "score" is the leg's own (L2 distance, BM25 score, RRF value)
     optional patient_id / from_date / to_date / include_knowledge_base scope the search to
     one patient's chunks (inside the window) plus, unless excluded, the knowledge base
 """
@@ -39,6 +41,7 @@ from ..config import Settings
 from ..index import faiss_io
 from ..index.flat import FlatIndex  # noqa: F401  (the default store type)
 from ..index.hybrid import load_index, make_index
+from ..index.lexical import LexicalColumns, fetch_depth
 from ..index.scope import ScopeColumns, scope_request
 from ..pipeline.corpus import embed_records
 from ..schemas import SearchRequest
@@ -98,6 +101,9 @@ class SemanticIndexer:
         self.patients.rebuild(self.metadata)
         self.scopes = ScopeColumns(device)     # row tags / days of the scoped search
         self.scopes.rebuild(self.metadata)
+        # term columns of the lexical / hybrid search: built by the first such request
+        # (ensure_lexical), at start-up with LEXICAL_INDEX=1; kept in step once they exist
+        self.lexical: LexicalColumns | None = None
         self.lock = threading.RLock()
         self.on_indexed = on_indexed  # callback(doc_id) e.g. docs DB status -> INDEXED
         self._ch = None
@@ -130,6 +136,7 @@ class SemanticIndexer:
                 self.metadata = metadata_io.read_metadata(self.meta_path)
                 self.patients.rebuild(self.metadata)
                 self.scopes.rebuild(self.metadata)
+                self._lexical_rebuild()
                 if len(self.metadata) != self.index.ntotal:
                     raise RuntimeError(f"index/metadata mismatch: {self.index.ntotal} vs {len(self.metadata)}")
                 covered = read_snapshot_marker(self.marker_path)["wal_seq"]
@@ -139,6 +146,7 @@ class SemanticIndexer:
                 self.metadata = []
                 self.patients.rebuild(self.metadata)
                 self.scopes.rebuild(self.metadata)
+                self._lexical_rebuild()
                 if build_if_missing:
                     recs = kb_records_from_dir(self.st.default_data_dir) or synthetic_kb_records()
                     self.add_records(recs, log=False)
@@ -150,6 +158,7 @@ class SemanticIndexer:
                     self.metadata.extend(recs)
                     self.patients.extend(self.metadata)
                     self.scopes.extend(self.metadata)
+                    self._lexical_extend()
                     replayed += len(recs)
                 if replayed:
                     logger.info("replayed %d vectors from the write-ahead log", replayed)
@@ -157,7 +166,27 @@ class SemanticIndexer:
                     dirty = True
             if dirty:
                 self.save_state()
+            if self.st.lexical_index:
+                self.ensure_lexical()
         return self
+
+    # ------------------------------------------------------------------ lexical columns
+    def ensure_lexical(self) -> LexicalColumns:
+        """The BM25 term columns of the metadata list, built on the first call."""
+        with self.lock:
+            if self.lexical is None:
+                cols = LexicalColumns(self.device)
+                cols.rebuild(self.metadata)
+                self.lexical = cols
+            return self.lexical
+
+    def _lexical_extend(self) -> None:
+        if self.lexical is not None:
+            self.lexical.extend(self.metadata)
+
+    def _lexical_rebuild(self) -> None:
+        if self.lexical is not None:
+            self.lexical.rebuild(self.metadata)
 
     def save_state(self) -> None:
         with self.lock:
@@ -193,6 +222,7 @@ class SemanticIndexer:
             self.metadata.extend(recs)
             self.patients.extend(self.metadata)
             self.scopes.extend(self.metadata)
+            self._lexical_extend()
             self.version += 1
         return len(recs)
 
@@ -271,12 +301,18 @@ class SemanticIndexer:
 
     # ------------------------------------------------------------------ query
     @torch.inference_mode()
-    def search(self, query: str, k: int = 3, scope: dict | None = None) -> list[dict]:
+    def search(self, query: str, k: int = 3, scope: dict | None = None, mode: str | None = None) -> list[dict]:
         """``scope``: None, or a scope request (index/scope.py ``scope_request``) -- the hits
-        then come from that patient / window (and the knowledge base unless excluded) only."""
-        q = self.encoder.encode(self.tok.encode_batch([query]))
+        then come from that patient / window (and the knowledge base unless excluded) only.
+        ``mode``: None / ``"dense"`` (the kNN search, ``score`` = L2 distance), ``"lexical"``
+        (BM25, ``score`` = BM25 score) or ``"hybrid"`` (reciprocal rank fusion of both at depth
+        ``HYBRID_FETCH_K``, ``score`` = RRF value)."""
+        # the lexical mode never uses the embedding
+        q = None if mode == "lexical" else self.encoder.encode(self.tok.encode_batch([query]))
         with self.lock:
-            if scope is None:
+            if mode is not None and mode != "dense":
+                D, I = self._search_mode(q, query, k, scope, mode)
+            elif scope is None:
                 D, I = self.index.search(q, k)
             else:
                 D, I = self.index.search_scoped(q, k, self.scopes, self.scopes.scope_rows([scope]))
@@ -293,6 +329,23 @@ class SemanticIndexer:
                     out.append({"id": i, "score": d, "text": m.get("text_content", ""), "source": m.get("source"),
                                 "type": m.get("type"), "doc_id": str(m.get("doc_id"))})
             return out
+
+    def _search_mode(self, q, query: str, k: int, scope, mode: str):
+        from .. import ops
+
+        if mode not in ("lexical", "hybrid"):
+            raise ValueError(f"search mode must be dense, lexical or hybrid, got {mode!r}")
+        if not 1 <= k <= 64:
+            raise ValueError("lexical / hybrid search serves k in 1..64")
+        lex = self.ensure_lexical()
+        cols, rows = (self.scopes, self.scopes.scope_rows([scope])) if scope is not None else (None, None)
+        qt, qw, avgdl = lex.query_rows([query])
+        if mode == "lexical":
+            return self.index.search_lexical(lex, qt, qw, avgdl, k, scope_cols=cols, scope=rows)
+        depth = fetch_depth(k)
+        _, Id = self.index.search(q, depth) if scope is None else self.index.search_scoped(q, depth, cols, rows)
+        _, Il = self.index.search_lexical(lex, qt, qw, avgdl, depth, scope_cols=cols, scope=rows)
+        return ops.rank_fuse(Id, Il, torch.full((1,), 2, dtype=torch.int32, device=Id.device), k)
 
     def patient_snippets(self, patient_id: str, from_date=None, to_date=None, focus=None, limit: int = 20) -> list[dict]:
         """The patient's chunks, optionally restricted to notes dated in [from_date, to_date]
@@ -331,7 +384,8 @@ def create_app(indexer: SemanticIndexer) -> FastAPI:
     def stats():
         idx = indexer.index
         return {"ntotal": idx.ntotal if idx is not None else 0, "dim": idx.d if idx is not None else None,
-                "metric": idx.metric if idx is not None else None, "version": indexer.version}
+                "metric": idx.metric if idx is not None else None, "version": indexer.version,
+                "lexical": indexer.lexical.stats() if indexer.lexical is not None else None}
 
     @app.post("/api/search")
     def search(req: SearchRequest):
@@ -341,6 +395,12 @@ def create_app(indexer: SemanticIndexer) -> FastAPI:
             scope = scope_request(req.patient_id, req.from_date, req.to_date, req.include_knowledge_base)
         except ValueError as e:
             return JSONResponse(status_code=422, content={"detail": str(e)})
+        mode = req.search_mode or indexer.st.retrieval_mode
+        if mode != "dense":
+            try:
+                return indexer.search(req.query, req.k, scope, mode)
+            except (ValueError, NotImplementedError) as e:
+                return JSONResponse(status_code=422, content={"detail": str(e)})
         if scope is None:
             return indexer.search(req.query, req.k)
         return indexer.search(req.query, req.k, scope)

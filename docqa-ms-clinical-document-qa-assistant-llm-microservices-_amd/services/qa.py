@@ -6,6 +6,8 @@ Contract (llm-qa/main.py:108-126 and synthese-comparative/core/llm_client.py:42-
                             include_knowledge_base scope the retrieval to one patient's
                             chunks (inside the window) plus, unless excluded, the knowledge
                             base (index/scope.py); 422 on an unparseable date
+                            optional search_mode dense | lexical | hybrid (default
+                            RETRIEVAL_MODE): kNN, BM25 or their rank fusion; 422 on another
                             503 {"detail": "Index non chargé."} when no index is loaded
   POST /api/llm/summarize   {"prompt"}   -> {"summary"}   (expected by synthese, missing
                             in the reference; served here)
@@ -45,16 +47,24 @@ from ..utils import tracing
 from ..utils.metrics import Metrics
 
 
-def ask_payload(question: str, scope: dict | None):
-    """The batcher payload of an ask: the plain question when it has no scope."""
-    return question if scope is None else {"question": question, "scope": scope}
+def ask_payload(question: str, scope: dict | None, mode: str | None = None):
+    """The batcher payload of an ask: the plain question when it has no scope and the dense
+    retrieval mode."""
+    if mode == "dense":
+        mode = None
+    if scope is None and mode is None:
+        return question
+    return {"question": question, "scope": scope, "mode": mode}
 
 
-def _ask_parts(asks) -> tuple[list[str], list | None]:
-    """(questions, scopes) of queued asks; scopes is None when no ask carries one."""
+def _ask_parts(asks) -> tuple[list[str], list | None, list | None]:
+    """(questions, scopes, modes) of queued asks; scopes is None when no ask carries one,
+    modes is None when every ask is dense."""
     qs = [it[1]["question"] if isinstance(it[1], dict) else it[1] for it in asks]
     scopes = [it[1].get("scope") if isinstance(it[1], dict) else None for it in asks]
-    return qs, (scopes if any(s is not None for s in scopes) else None)
+    modes = [(it[1].get("mode") if isinstance(it[1], dict) else None) or "dense" for it in asks]
+    return (qs, scopes if any(s is not None for s in scopes) else None,
+            modes if any(m != "dense" for m in modes) else None)
 
 
 def penalty_defaults(st: Settings) -> dict:
@@ -106,9 +116,12 @@ class DynamicBatcher:
         sums = [b for b in batch if b[0] == "summarize"]
         try:
             if asks:
-                qs, scopes = _ask_parts(asks)
-                res = (self.pipe.answer_batch(qs, self._params()) if scopes is None
-                       else self.pipe.answer_batch(qs, self._params(), scopes=scopes))
+                qs, scopes, modes = _ask_parts(asks)
+                if modes is not None:
+                    res = self.pipe.answer_batch(qs, self._params(), scopes=scopes, modes=modes)
+                else:
+                    res = (self.pipe.answer_batch(qs, self._params()) if scopes is None
+                           else self.pipe.answer_batch(qs, self._params(), scopes=scopes))
                 for (_, _, f, t0), r in zip(asks, res):
                     self.metrics.observe("ask_latency_s", time.perf_counter() - t0)
                     f.set_result({"answer": r.answer, "sources": r.sources})
@@ -288,9 +301,12 @@ class ContinuousBatcher:
         sums = [it for it in items if it[0] == "summarize"]
         if asks:
             tp0 = time.perf_counter()
-            qs, scopes = _ask_parts(asks)
+            qs, scopes, modes = _ask_parts(asks)
             qemb = pipe.embed(qs)
-            _, I = pipe.index.search(qemb, pipe.k) if scopes is None else pipe.search(qemb, scopes)
+            if modes is not None:
+                _, I = pipe.search(qemb, scopes, modes, qs)
+            else:
+                _, I = pipe.index.search(qemb, pipe.k) if scopes is None else pipe.search(qemb, scopes)
             I = pipe._host_ids(I)
             prompts = pipe.build_prompts(qs, I)
             te = time.perf_counter()
@@ -388,7 +404,8 @@ class ReplicaRouter:
                 if kind == "ask":      # remote replicas get the scope fields, the local batcher the scope
                     local = ask_payload(local, scope_request(payload.get("patient_id"), payload.get("from_date"),
                                                              payload.get("to_date"),
-                                                             payload.get("include_knowledge_base", True)))
+                                                             payload.get("include_knowledge_base", True)),
+                                        payload.get("search_mode"))
                 return await asyncio.wrap_future(self.local.submit(kind, local))
             r = await self.client.post(self.targets[i] + path, json=payload)
             return JSONResponse(status_code=r.status_code, content=r.json())
@@ -425,14 +442,19 @@ def create_app(pipeline=None, settings: Settings | None = None, lockstep=None,
             scope = scope_request(query.patient_id, query.from_date, query.to_date, query.include_knowledge_base)
         except ValueError as e:
             return JSONResponse(status_code=422, content={"detail": str(e)})
+        mode = query.search_mode or st.retrieval_mode
+        if mode not in ("dense", "lexical", "hybrid"):
+            return JSONResponse(status_code=422, content={"detail": f"RETRIEVAL_MODE: unknown mode {mode!r}"})
         metrics.inc("ask_requests")
         if router is not None:
             payload = {"question": query.question}
             if scope is not None:
                 payload.update(patient_id=query.patient_id, from_date=query.from_date, to_date=query.to_date,
                                include_knowledge_base=query.include_knowledge_base)
+            if mode != "dense":     # explicit, so every replica answers alike whatever its default
+                payload["search_mode"] = mode
             return await router.call("ask", "/ask/", payload, "question")
-        fut = app.state.batcher.submit("ask", ask_payload(query.question, scope))
+        fut = app.state.batcher.submit("ask", ask_payload(query.question, scope, mode))
         return await asyncio.wrap_future(fut)
 
     @app.post("/api/llm/summarize", response_model=SummarizeResponse)

@@ -150,7 +150,9 @@ class DocQAStack:
                                         self.engine, self.chat_tok, k=self.st.top_k,
                                         max_prompt_tokens=ctx - self.st.max_new_tokens - 8)
             # the owner of the (index, metadata) pair keeps the scoped search's row attributes
-            self.pipeline.scopes = (self.indexer if self.indexer is not None else self.follower).scopes
+            owner = self.indexer if self.indexer is not None else self.follower
+            self.pipeline.scopes = owner.scopes
+            self.pipeline.lexical_owner = owner      # builds the BM25 term columns on first use
             self.qa_app = qa.create_app(self.pipeline, self.st, lockstep=opts.qa_lockstep,
                                         replicas=list(opts.qa_replicas) or None)
         if "ingest" in svc:
