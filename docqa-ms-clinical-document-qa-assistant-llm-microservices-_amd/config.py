@@ -39,6 +39,30 @@ def env_int(name: str, default: int) -> int:
         return default
 
 
+def env_float(name: str, default: float) -> float:
+    try:
+        return float(os.getenv(name, str(default)))
+    except ValueError:
+        return default
+
+
+def mmr_request(search_type, lambda_mult, fetch_k, st: "Settings"):
+    """A request's ``search_type`` / ``lambda_mult`` / ``fetch_k`` (LangChain's retriever
+    arguments; ``None`` = the service default) -> ``None`` for the similarity search or
+    ``(lambda_mult, fetch_k)`` for MMR.  ValueError on an unknown type, a ``lambda_mult``
+    outside [0, 1] or ``fetch_k < 1`` (the services answer 422)."""
+    kind = search_type or st.retrieval_search_type
+    if kind not in ("similarity", "mmr"):
+        raise ValueError(f"search_type must be similarity or mmr, got {kind!r}")
+    lam = st.mmr_lambda if lambda_mult is None else float(lambda_mult)
+    fk = st.mmr_fetch_k if fetch_k is None else int(fetch_k)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_mult must be in [0, 1], got {lam!r}")
+    if fk < 1:
+        raise ValueError(f"fetch_k must be >= 1, got {fk!r}")
+    return (lam, fk) if kind == "mmr" else None
+
+
 @dataclass
 class Settings:
     # transport / infra (reference names)
@@ -97,6 +121,11 @@ class Settings:
     # instead of on the first lexical / hybrid request (index/lexical.py)
     retrieval_mode: str = field(default_factory=lambda: os.getenv("RETRIEVAL_MODE", "dense"))
     lexical_index: bool = field(default_factory=lambda: env_bool("LEXICAL_INDEX", "false"))
+    # LangChain's retriever search_type of requests that carry none: similarity | mmr (maximal
+    # marginal relevance, ops.mmr_select), with its lambda_mult and fetch_k (clamped to k..64)
+    retrieval_search_type: str = field(default_factory=lambda: os.getenv("RETRIEVAL_SEARCH_TYPE", "similarity"))
+    mmr_lambda: float = field(default_factory=lambda: env_float("MMR_LAMBDA", 0.5))
+    mmr_fetch_k: int = field(default_factory=lambda: env_int("MMR_FETCH_K", 20))
     max_new_tokens: int = field(default_factory=lambda: env_int("MAX_NEW_TOKENS", 256))
     temperature: float = field(default_factory=lambda: float(os.getenv("TEMPERATURE", "0")))
     # llama.cpp-style penalties over the last REPEAT_LAST_N tokens of prompt + output (neutral

@@ -1993,6 +1993,42 @@ std::tuple<at::Tensor, at::Tensor> rank_fuse(const at::Tensor& i_dense, const at
   return {out_f, out_i};
 }
 
+// maximal marginal relevance re-selection of ranked candidate lists (mmr.hip): xb fp32 / bf16
+// [N, d], cand int64 [nq, F <= 64], ncand int32 [nq], lam fp32 [nq] -> (S, I, P) [nq, k]
+std::tuple<at::Tensor, at::Tensor, at::Tensor> mmr_select(const at::Tensor& xb, const at::Tensor& xb_norms,
+                                                          const at::Tensor& xq, const at::Tensor& cand,
+                                                          const at::Tensor& ncand, const at::Tensor& lam,
+                                                          int64_t k) {
+  CHECK_GPU(xb); CHECK_GPU(xb_norms); CHECK_GPU(xq); CHECK_GPU(cand); CHECK_GPU(ncand); CHECK_GPU(lam);
+  CHECK_CONTIG(xb); CHECK_CONTIG(xb_norms); CHECK_CONTIG(xq); CHECK_CONTIG(cand); CHECK_CONTIG(ncand);
+  CHECK_CONTIG(lam); CHECK_I32(ncand);
+  TORCH_CHECK(xb.scalar_type() == at::kFloat || xb.scalar_type() == at::kBFloat16, "mmr_select: xb must be fp32 or bf16");
+  TORCH_CHECK(xb.dim() == 2 && xq.dim() == 2 && xq.scalar_type() == at::kFloat && xq.size(1) == xb.size(1),
+              "mmr_select: xb [N, d], xq fp32 [nq, d]");
+  TORCH_CHECK(xb_norms.scalar_type() == at::kFloat && xb_norms.numel() == xb.size(0),
+              "mmr_select: xb_norms must be fp32 [N]");
+  const int64_t nq = xq.size(0);
+  TORCH_CHECK(cand.scalar_type() == at::kLong && cand.dim() == 2 && cand.size(0) == nq,
+              "mmr_select: cand must be int64 [nq, F]");
+  TORCH_CHECK(ncand.numel() == nq && lam.scalar_type() == at::kFloat && lam.numel() == nq,
+              "mmr_select: ncand int32 [nq], lam fp32 [nq]");
+  const int64_t F = cand.size(1), d = xb.size(1);
+  const bool bf = xb.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(k >= 1 && k <= F && F <= 64, "mmr_select: 1 <= k <= F <= 64");
+  TORCH_CHECK(d > 0 && d < (int64_t(1) << 31) && d % (bf ? 16 : 8) == 0,
+              "mmr_select: d must be a multiple of 8 (fp32) / 16 (bf16)");
+  TORCH_CHECK(nq < (int64_t(1) << 31), "mmr_select: nq must be < 2^31");
+  c10::DeviceGuard g(xq.device());
+  auto out_s = at::empty({nq, k}, xq.options());
+  auto out_i = at::empty({nq, k}, xq.options().dtype(at::kLong));
+  auto out_p = at::empty({nq, k}, xq.options().dtype(at::kInt));
+  CHECK_RC(docqa_mmr_select(xb.data_ptr(), xb_norms.data_ptr<float>(), xb.size(0), (int)d, bf ? 1 : 0,
+                            xq.data_ptr<float>(), cand.data_ptr<int64_t>(), (int)F, ncand.data_ptr<int>(),
+                            lam.data_ptr<float>(), (int)nq, (int)k, out_s.data_ptr<float>(),
+                            out_i.data_ptr<int64_t>(), out_p.data_ptr<int>(), stream()), "mmr_select");
+  return {out_s, out_i, out_p};
+}
+
 // IVF coarse quantizer, wide probes: int64 [nq, nprobe] nearest centroids (ascending, ties
 // to the lower id) for nprobe <= 512
 // exact fp32 x @ w^T on the coarse quantizer's MFMA tiles (the IVF-PQ query pre-rotation)
@@ -2265,6 +2301,8 @@ TORCH_LIBRARY(docqa, m) {
         "float avgdl, float k1, float b, Tensor? tags, Tensor? days, Tensor? scope, int id_offset) "
         "-> (Tensor, Tensor)");
   m.def("rank_fuse(Tensor i_dense, Tensor i_lex, Tensor mode, int k, int c) -> (Tensor, Tensor)");
+  m.def("mmr_select(Tensor xb, Tensor xb_norms, Tensor xq, Tensor cand, Tensor ncand, Tensor lam, int k) "
+        "-> (Tensor, Tensor, Tensor)");
   m.def("coarse_probes(Tensor xq, Tensor cent, Tensor cnorm, int nprobe) -> Tensor");
   m.def("fp32_gemm_nt(Tensor x, Tensor w) -> Tensor");
   m.def("ivfpq_search(Tensor xq, Tensor centroids, Tensor pq, Tensor codes, Tensor ids, "
@@ -2385,6 +2423,7 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("knn_scoped", &knn_scoped);
   m.impl("bm25_topk", &bm25_topk);
   m.impl("rank_fuse", &rank_fuse);
+  m.impl("mmr_select", &mmr_select);
   m.impl("pool_l2", &pool_l2);
   m.impl("ivfpq_search", &ivfpq_search);
   m.impl("ivfpq_search_pt", &ivfpq_search_pt);

@@ -313,6 +313,12 @@ int docqa_bm25_topk(const int64_t* row_ptr, const int* terms, const uint8_t* tfs
 // per query: first k of either ranked id list (mode 0 / 1) or their reciprocal rank fusion (2)
 int docqa_rank_fuse(const int64_t* i_dense, int ld, const int64_t* i_lex, int ll, const int* mode, int nq,
                     int k, int c, float* out_f, int64_t* out_i, hipStream_t s);
+// maximal marginal relevance re-selection (mmr.hip): per query k picks out of cand [nq, F <= 64]
+// (the first ncand[q] entries, ids in [0, N)) by lam * cos(q, c) - (1 - lam) * max cos(c, picked);
+// lam < 0: the first k entries pass through.  out_s / out_i / out_p [nq, k]
+int docqa_mmr_select(const void* xb, const float* norms, int64_t N, int d, int is_bf16, const float* xq,
+                     const int64_t* cand, int F, const int* ncand, const float* lam, int nq, int k,
+                     float* out_s, int64_t* out_i, int* out_p, hipStream_t s);
 
 int docqa_ivfpq_search(const float* xq, const float* centroids, const float* pq,
                        const uint8_t* codes, const int64_t* ids, const int64_t* list_off,

@@ -165,6 +165,26 @@ class FlatIndex:
             return ops.bm25_topk(bufs[0][: n + 1], bufs[1], bufs[2], bufs[3][:n], qterms, qweights, k, avgdl,
                                  tags=tags, days=days, scope=scope, id_offset=id_offset)
 
+    def mmr_select(self, xq, cand, ncand, lam, k: int):
+        """Maximal marginal relevance re-selection (``ops.mmr_select``) of ranked row ids
+        ``cand`` int64 [nq, F] -- a search's hits over these rows -- against the stored vectors:
+        -> (S, I, P) [nq, k].  Ids outside ``[0, ntotal)`` are no candidates."""
+        xq = torch.as_tensor(xq)
+        if xq.dim() == 1:
+            xq = xq[None]
+        xq = xq.to(self.device, dtype=torch.float32)
+        cand = torch.as_tensor(cand).to(self.device, dtype=torch.long)
+        ncand = torch.as_tensor(ncand).to(self.device, dtype=torch.int32)
+        lam = torch.as_tensor(lam).to(self.device, dtype=torch.float32)
+        with self._lock:
+            xb, nm = self._xb, self._norms
+            if xb.is_cuda:
+                # as in search(): the kernel may run on a side stream while these are dropped
+                s = torch.cuda.current_stream(self.device)
+                xb.record_stream(s)
+                nm.record_stream(s)
+            return ops.mmr_select(xb[: self.ntotal], nm[: self.ntotal], xq, cand, ncand, lam, k)
+
     def reconstruct(self, i: int) -> np.ndarray:
         return self._xb[i].float().cpu().numpy()
 

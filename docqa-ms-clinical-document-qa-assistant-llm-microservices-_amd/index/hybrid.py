@@ -132,6 +132,11 @@ class IVFPQRefineIndex:
             return self.flat.search_lexical(cols, qterms, qweights, avgdl, k, scope_cols=scope_cols, scope=scope,
                                             id_offset=id_offset)
 
+    def mmr_select(self, xq, cand, ncand, lam, k: int):
+        """The re-selection reads the exact vectors, trained or not."""
+        with self._lock:
+            return self.flat.mmr_select(xq, cand, ncand, lam, k)
+
     def reconstruct(self, i: int) -> np.ndarray:
         return self.flat.reconstruct(i)
 

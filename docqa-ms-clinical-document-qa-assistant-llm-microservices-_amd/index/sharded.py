@@ -224,6 +224,11 @@ class ShardedIndex:
             "Document frequencies and the average length would have to agree across ranks, and "
             "no service builds a sharded index. That belongs with sharding the deployed index.")
 
+    def mmr_select(self, xq, cand, ncand, lam, k: int):
+        raise NotImplementedError(
+            "The candidates' vectors live on the ranks that hold their rows, and no service builds "
+            "a sharded index. That belongs with sharding the deployed index.")
+
     def _search(self, xq: torch.Tensor, k: int, **kw):
         nq = xq.shape[0]
         dev = xq.device

@@ -1977,6 +1977,29 @@ def rank_fuse(I_dense, I_lex, mode, k: int, c: int = 60):
     return ref.rank_fuse(I_dense, I_lex, mode, k, c)
 
 
+def mmr_select(xb, xb_norms, xq, cand, ncand, lam, k: int):
+    """Maximal marginal relevance re-selection of ranked candidate lists (LangChain's
+    ``search_type="mmr"``): per query ``k`` picks out of ``cand`` int64 [nq, F] (best first; the
+    first ``ncand[q]`` entries with an id in ``[0, N)``), greedily by ``lam * cos(q, c) -
+    (1 - lam) * max cos(c, picked)``, cosines in fp32 whatever the index metric; ``lam`` fp32
+    [nq], negative = the row's first k entries pass through.  -> (S fp32, I int64, P int32
+    [nq, k]): the winning value, the id and the position in ``cand`` of every pick, 0 / -1 /
+    -1 in missing slots; see ``reference.mmr_select``.  GPU: one launch, one workgroup per
+    query (csrc/kernels/mmr.hip), no host sync.  Outside its envelope (``1 <= k <= F <= 64``,
+    ``d`` a multiple of 8 / 16 for fp32 / bf16 rows, no other row dtype) and with
+    ``DOCQA_MMR=0`` (kill switch) the fp32 reference runs on the same device instead of
+    failing."""
+    if _gpu(xq) and os.environ.get("DOCQA_MMR", "1") != "0":
+        bf = xb.dtype == torch.bfloat16
+        d, F = int(xb.shape[1]), int(cand.shape[1])
+        if (1 <= k <= F <= 64 and (bf or xb.dtype == torch.float32) and d > 0 and d % (16 if bf else 8) == 0
+                and xq.shape[0] > 0):
+            return _native().mmr_select(xb.contiguous(), xb_norms.float().contiguous(), xq.float().contiguous(),
+                                        cand.long().contiguous(), ncand.int().contiguous(),
+                                        lam.float().contiguous(), k)
+    return ref.mmr_select(xb, xb_norms, xq, cand, ncand, lam, k)
+
+
 def fp32_matmul_nt(x, w):
     """Exact fp32 ``x @ w.T`` on the coarse quantizer's MFMA tiles (coarse.hip) -- the IVF-PQ
     query pre-rotation on the GPU without a library GEMM; torch on the CPU."""

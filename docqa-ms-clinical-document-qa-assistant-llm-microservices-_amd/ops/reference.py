@@ -626,6 +626,65 @@ def rank_fuse(I_dense, I_lex, mode, k, c=60):
     return (num / den).to(dev), I.to(dev)
 
 
+def mmr_select(xb, xb_norms, xq, cand, ncand, lam, k):
+    """Maximal marginal relevance over ranked candidate lists (LangChain's
+    ``maximal_marginal_relevance``, all fp32).  cand int64 [nq, F] (best first; only the first
+    ``ncand[q]`` entries with an id in ``[0, N)`` are candidates), lam fp32 [nq]:
+
+        cos(a, b) = dot(a, b) / sqrt(|a|^2 * |b|^2), 0 when that root is 0
+        pick 0    = argmax cos(q, c)
+        pick t    = argmax over the unpicked c of  lam * cos(q, c) - (1 - lam) * max_s cos(c, s)
+
+    ``|row|^2`` is ``xb_norms``; ties go to the earlier position; min(k, candidates) picks.
+    ``lam < 0``: the row's first k entries pass through (S = 0, P = 0..k-1).  -> (S fp32 = the
+    value that won each pick, I int64 = its id, P int32 = its position in ``cand``), missing
+    slots 0 / -1 / -1.  The same id at two positions is two candidates."""
+    dev = xq.device
+    nq, F = cand.shape
+    N = xb.shape[0]
+    S = torch.zeros((nq, k), dtype=torch.float32, device=dev)
+    I = torch.full((nq, k), -1, dtype=torch.long, device=dev)
+    P = torch.full((nq, k), -1, dtype=torch.int32, device=dev)
+    if nq == 0:
+        return S, I, P
+    cand = cand.long()
+    lam = lam.float().reshape(nq)
+    kk = min(k, F)
+    off = lam < 0
+    pos = torch.arange(F, device=dev)
+    I[:, :kk] = torch.where(off[:, None], cand[:, :kk], I[:, :kk])
+    P[:, :kk] = torch.where(off[:, None], pos[None, :kk].int(), P[:, :kk])
+    if N == 0 or F == 0:
+        return S, I, P
+    valid = (pos[None, :] < ncand.reshape(nq, 1)) & (cand >= 0) & (cand < N) & ~off[:, None]
+    idx = cand.clamp(0, N - 1)
+    rows = xb[idx.reshape(-1)].float().reshape(nq, F, -1) * valid[:, :, None]
+    nb = xb_norms.float()[idx] * valid
+    q = xq.float()
+    qn = (q * q).sum(1)
+
+    def cosine(dot, na, nb_):
+        den = torch.sqrt(na * nb_)
+        return torch.where(den > 0, dot / den, torch.zeros_like(dot))
+
+    rel = cosine(torch.bmm(rows, q[:, :, None])[:, :, 0], qn[:, None], nb)
+    sim = cosine(torch.bmm(rows, rows.transpose(1, 2)), nb[:, :, None], nb[:, None, :])
+    avail = valid.clone()
+    red = torch.zeros_like(rel)
+    lm, oml = lam[:, None], (1.0 - lam)[:, None]
+    ar = torch.arange(nq, device=dev)
+    for t in range(kk):
+        score = rel if t == 0 else lm * rel - oml * red
+        p = torch.where(avail, score, torch.full_like(score, -math.inf)).argmax(1)
+        on = avail.any(1)
+        S[:, t] = torch.where(on, score[ar, p], S[:, t])
+        I[:, t] = torch.where(on, cand[ar, p], I[:, t])
+        P[:, t] = torch.where(on, p.int(), P[:, t])
+        avail[ar, p] = False
+        red = sim[ar, p] if t == 0 else torch.maximum(red, sim[ar, p])
+    return S, I, P
+
+
 def pool_l2(h, cu_seqlens, mean, normalize):
     cu = cu_seqlens.tolist()
     out = torch.zeros(len(cu) - 1, h.shape[-1], dtype=torch.float32, device=h.device)

@@ -162,13 +162,18 @@ class RAGPipeline:
         return self.lexical
 
     def search(self, qemb: torch.Tensor, scopes: list | None = None, modes: list | None = None,
-               texts: list | None = None):
+               texts: list | None = None, mmr: list | None = None):
         """(D, I) of the embedded questions' top-k.  ``scopes``: per question ``None`` or a
         scope request (index/scope.py: patient_id, from_date, to_date,
         include_knowledge_base); a batch without any takes the unscoped search, a mixed
         batch is one scoped launch (``None`` = the any-scope row).  ``modes``: per question
         ``"dense"``, ``"lexical"`` or ``"hybrid"`` (``texts``: the questions, needed by the last
-        two); ``None`` or all dense is the dense search alone."""
+        two); ``None`` or all dense is the dense search alone.  ``mmr``: per question ``None`` or
+        ``(lambda_mult, fetch_k)`` -- the k hits are then re-selected for diversity out of the
+        question's first ``fetch_k`` (:meth:`_search_mmr`); ``None`` or all ``None`` runs exactly
+        the launches above."""
+        if mmr is not None and any(m is not None for m in mmr):
+            return self._search_mmr(qemb, scopes, modes, texts, mmr)
         if modes is not None and any(m != "dense" for m in modes):
             return self._search_modes(qemb, scopes, modes, texts)
         if scopes is None or all(s is None for s in scopes):
@@ -213,12 +218,85 @@ class RAGPipeline:
         m = mode[:, None]
         return torch.where(m == 0, Dd[:, :k], torch.where(m == 1, Sl[:, :k], F)), I
 
-    def retrieve(self, questions: list[str], scopes: list | None = None, modes: list | None = None):
+    def _search_mmr(self, qemb, scopes, modes, texts, mmr):
+        """A batch with a maximal-marginal-relevance question (LangChain's
+        ``search_type="mmr"``): the legs run at depth ``max(k, max fetch_k)`` (with a lexical or
+        hybrid question both legs at ``max(fetch_depth(k), that)`` and ``ops.rank_fuse`` returns
+        that many ids), then one ``mmr_select`` launch re-selects k per question out of its own
+        first ``fetch_k`` candidates by ``lambda_mult * cos(q, c) - (1 - lambda_mult) * max
+        cos(c, picked)``.  Questions without MMR carry ``lam = -1`` and keep their first k; their
+        rank fusion sees the leg depth it sees without MMR in the batch.  The relevance term is
+        the cosine to the question's embedding in every mode; scopes apply to the candidates.
+        D is the leg's own score of each picked row (gathered by position on the device), in
+        pick order; no host sync."""
+        nq, k = qemb.shape[0], self.k
+        if len(mmr) != nq:
+            raise ValueError("one mmr entry per question")
+        if k > 64:
+            raise ValueError("mmr search serves k <= 64")
+        lam_h, fk_h = [], []
+        for m in mmr:
+            if m is None:
+                lam_h.append(-1.0)
+                fk_h.append(k)
+                continue
+            lm, fk = float(m[0]), int(m[1])
+            if not 0.0 <= lm <= 1.0:
+                raise ValueError(f"lambda_mult must be in [0, 1], got {m[0]!r}")
+            if fk < 1:
+                raise ValueError(f"fetch_k must be >= 1, got {m[1]!r}")
+            lam_h.append(lm)
+            fk_h.append(min(64, max(k, fk)))
+        F = max(fk_h)
+        scoped = scopes is not None and any(s is not None for s in scopes)
+        if scoped and len(scopes) != nq:
+            raise ValueError("one scope per question")
+        cols = rows = None
+        if scoped:
+            cols = self._scope_cols(qemb.device)
+            rows = cols.scope_rows(scopes)
+        if modes is not None and any(m != "dense" for m in modes):
+            if texts is None or len(texts) != nq or len(modes) != nq:
+                raise ValueError("one mode and one question text per question")
+            bad = [m for m in modes if m not in SEARCH_MODES]
+            if bad:
+                raise ValueError(f"search mode must be one of {SEARCH_MODES}, got {bad[0]!r}")
+            from ..index.lexical import fetch_depth
+
+            base = fetch_depth(k)
+            depth = max(base, F)
+            lex = self._lexical_cols(qemb.device)
+            Dd, Id = (self.index.search_scoped(qemb, depth, cols, rows) if scoped
+                      else self.index.search(qemb, depth))
+            qt, qw, avgdl = lex.query_rows(list(texts))
+            Sl, Il = self.index.search_lexical(lex, qt, qw, avgdl, depth, scope_cols=cols, scope=rows)
+            dev = Id.device
+            mode = torch.tensor([SEARCH_MODES.index(m) for m in modes], dtype=torch.int32).to(dev)
+            # every question fuses the leg depth it asked for: fetch_depth(k) without MMR
+            own = torch.tensor([base if m is None else max(base, f) for m, f in zip(mmr, fk_h)]).to(dev)
+            past = torch.arange(depth, device=dev)[None, :] >= own[:, None]
+            Fv, C = ops.rank_fuse(Id.masked_fill(past, -1), Il.masked_fill(past, -1), mode, F)
+            m = mode[:, None]
+            Dc = torch.where(m == 0, Dd[:, :F], torch.where(m == 1, Sl[:, :F], Fv))
+            miss = torch.tensor([(3.4028234663852886e38, -3.4028234663852886e38, 0.0)[SEARCH_MODES.index(md)]
+                                 for md in modes], dtype=torch.float32).to(dev)
+        else:
+            Dc, C = (self.index.search_scoped(qemb, F, cols, rows) if scoped else self.index.search(qemb, F))
+            dev = C.device
+            miss = torch.full((nq,), 3.4028234663852886e38, dtype=torch.float32, device=dev)
+        lam = torch.tensor(lam_h, dtype=torch.float32).to(dev)
+        ncand = torch.tensor(fk_h, dtype=torch.int32).to(dev)
+        _, I, P = self.index.mmr_select(qemb, C, ncand, lam, k)
+        D = torch.gather(Dc, 1, P.clamp(min=0).long())
+        return torch.where(P >= 0, D, miss[:, None]), I
+
+    def retrieve(self, questions: list[str], scopes: list | None = None, modes: list | None = None,
+                 mmr: list | None = None):
         """(D, I) of the questions' top-k.  On a sharded index the hits are checked for a
         failed cross-rank gather here (one host sync on the search's ids) so no caller can
         use stale peer rows unchecked."""
         q = self.embed(questions)
-        D, I = self.search(q, scopes, modes, questions)
+        D, I = self.search(q, scopes, modes, questions, mmr)
         if getattr(self.index, "check_gather", None) is not None:
             self._host_ids(I)
         return D, I
@@ -303,7 +381,8 @@ class RAGPipeline:
 
     @torch.inference_mode()
     def answer_batch(self, questions: list[str], params: SamplingParams | None = None,
-                     scopes: list | None = None, modes: list | None = None) -> list[Answer]:
+                     scopes: list | None = None, modes: list | None = None,
+                     mmr: list | None = None) -> list[Answer]:
         params = params or SamplingParams(stop_on_eos=True)
         t = StageTimes()
         t0 = time.perf_counter()
@@ -312,7 +391,7 @@ class RAGPipeline:
             self._sync()
         t1 = time.perf_counter()
         with tracing.span("rag.search", n=len(questions), k=self.k):
-            D, I = self.search(qemb, scopes, modes, questions)
+            D, I = self.search(qemb, scopes, modes, questions, mmr)
             I = self._host_ids(I)  # host needs ids to assemble the prompts
         t2 = time.perf_counter()
         with tracing.span("rag.prompt", n=len(questions)):
@@ -331,13 +410,13 @@ class RAGPipeline:
         return res
 
     def answer(self, question: str, params: SamplingParams | None = None, scope: dict | None = None,
-               mode: str | None = None) -> Answer:
+               mode: str | None = None, mmr: tuple | None = None) -> Answer:
         return self.answer_batch([question], params, None if scope is None else [scope],
-                                 None if mode is None else [mode])[0]
+                                 None if mode is None else [mode], None if mmr is None else [mmr])[0]
 
     # ------------------------------------------------------------------ pipelined
     @torch.inference_mode()
-    def _prepare(self, questions: list[str], stream, gate, params=None, scopes=None):
+    def _prepare(self, questions: list[str], stream, gate, params=None, scopes=None, mmr=None):
         """embed + kNN on a side HIP stream (held back by ``gate`` until the running
         generation is ``lead_steps`` from its end), then host-side prompt assembly and
         (``params`` given) the batch's KV-block reservation."""
@@ -354,14 +433,14 @@ class RAGPipeline:
                 evs[0].record(stream)
                 qemb = self.embed(questions)
                 evs[1].record(stream)
-                _, I = self.search(qemb, scopes)
+                _, I = self.search(qemb, scopes, mmr=mmr)
                 evs[2].record(stream)
                 I = self._host_ids(I)       # waits for this side stream only
             host = None
         else:
             qemb = self.embed(questions)
             tm = time.perf_counter()
-            _, I = self.search(qemb, scopes)
+            _, I = self.search(qemb, scopes, mmr=mmr)
             I = self._host_ids(I)
             host = (tm - t0, time.perf_counter() - tm)
         t1 = time.perf_counter()
@@ -380,7 +459,8 @@ class RAGPipeline:
 
     @torch.inference_mode()
     def answer_pipelined(self, batches: list[list[str]], params: SamplingParams | None = None,
-                         lead_steps: int | None = None, scopes: list | None = None):
+                         lead_steps: int | None = None, scopes: list | None = None,
+                         mmr: list | None = None):
         """Yield (answers, StageTimes, latency_s) per batch.  Batch i+1's embedding and
         kNN search run on a side HIP stream and its prompt assembly + KV reservation on a
         helper thread, released when batch i's decode is ``lead_steps`` steps from its
@@ -389,7 +469,8 @@ class RAGPipeline:
         detokenised on a second helper thread, so the GPU never waits on host work between
         batches.  Latency is measured on the GPU clock from the moment batch i+1's
         embedding may start to its answers being ready.  ``scopes``: per batch ``None`` or the
-        list of per-question scope requests (see :meth:`search`)."""
+        list of per-question scope requests, ``mmr``: per batch ``None`` or the list of per-question
+        ``(lambda_mult, fetch_k)`` entries (see :meth:`search`)."""
         import concurrent.futures as cf
 
         params = params or SamplingParams(stop_on_eos=True)
@@ -452,7 +533,8 @@ class RAGPipeline:
         with cf.ThreadPoolExecutor(1, thread_name_prefix="rag-prep") as ex, \
                 cf.ThreadPoolExecutor(1, thread_name_prefix="rag-collect") as col:
             sc = (lambda i: scopes[i]) if scopes is not None else (lambda i: None)
-            fut = ex.submit(self._prepare, batches[0], stream, None, params, sc(0)) if batches else None
+            mm = (lambda i: mmr[i]) if mmr is not None else (lambda i: None)
+            fut = ex.submit(self._prepare, batches[0], stream, None, params, sc(0), mm(0)) if batches else None
             fin = None
             try:
                 for i in range(len(batches)):
@@ -467,8 +549,9 @@ class RAGPipeline:
                     nxt = batches[i + 1] if i + 1 < len(batches) else None
 
                     nxt_sc = sc(i + 1) if nxt is not None else None
+                    nxt_mm = mm(i + 1) if nxt is not None else None
 
-                    def on_step(step, total, nxt=nxt, nxt_sc=nxt_sc):
+                    def on_step(step, total, nxt=nxt, nxt_sc=nxt_sc, nxt_mm=nxt_mm):
                         nonlocal fut, fin, pending
                         if pending is not None and fin is None:
                             p, pending = pending, None
@@ -478,7 +561,7 @@ class RAGPipeline:
                             if cuda:
                                 gate = torch.cuda.Event()
                                 gate.record()
-                            fut = ex.submit(self._prepare, nxt, stream, gate, params, nxt_sc)
+                            fut = ex.submit(self._prepare, nxt, stream, gate, params, nxt_sc, nxt_mm)
 
                     if reserved is None and pending is not None and len(prompts) <= eng.max_batch:
                         # no KV reservation (pool held by the batch in flight): collect that
@@ -492,7 +575,7 @@ class RAGPipeline:
                         h = None
                         outs = eng.generate(prompts, params, on_step=on_step)
                     if nxt is not None and fut is None:   # single-step generations
-                        fut = ex.submit(self._prepare, nxt, stream, None, params, nxt_sc)
+                        fut = ex.submit(self._prepare, nxt, stream, None, params, nxt_sc, nxt_mm)
                     if pending is not None:   # no decode step enqueued: collect batch i-1 now
                         p, pending = pending, None
                         fin = col.submit(finish, p)

@@ -15,6 +15,11 @@ from pydantic import BaseModel, Field
 # retrieval mode of a question: the dense kNN hits, the BM25 hits or their reciprocal rank
 # fusion; None = the service default (RETRIEVAL_MODE).  Any other value is a 422.
 SearchMode = Optional[Literal["dense", "lexical", "hybrid"]]
+# LangChain's retriever arguments (the reference's retriever is vector_store.as_retriever):
+# search_type "mmr" re-selects the k hits for diversity out of the first fetch_k (clamped to
+# k..64) with lambda_mult in [0, 1]; None = the service defaults (RETRIEVAL_SEARCH_TYPE,
+# MMR_LAMBDA, MMR_FETCH_K).  Anything else is a 422.
+SearchType = Optional[Literal["similarity", "mmr"]]
 
 
 # ---------------------------------------------------------------- llm-qa
@@ -27,6 +32,9 @@ class Query(BaseModel):
     to_date: Optional[str] = None
     include_knowledge_base: bool = True
     search_mode: SearchMode = None
+    search_type: SearchType = None
+    lambda_mult: Optional[float] = Field(default=None, ge=0.0, le=1.0)
+    fetch_k: Optional[int] = Field(default=None, ge=1)
 
 
 AskRequest = Query      # the reference's name for the /ask/ body is Query
@@ -68,6 +76,9 @@ class SearchRequest(BaseModel):
     to_date: Optional[str] = None
     include_knowledge_base: bool = True
     search_mode: SearchMode = None
+    search_type: SearchType = None
+    lambda_mult: Optional[float] = Field(default=None, ge=0.0, le=1.0)
+    fetch_k: Optional[int] = Field(default=None, ge=1)
 
 
 # ---------------------------------------------------------------- synthese-comparative

@@ -21,6 +21,9 @@ synthese-comparative/core/retrieval_client.py:72-91):
   POST /api/search {"query", "k"} -> hits;  GET /api/index/stats;  GET /health
     optional search_mode dense | lexical | hybrid (default RETRIEVAL_MODE): kNN, BM25 or their
     reciprocal rank fusion; "score" is the leg's own (L2 distance, BM25 score, RRF value)
+    optional search_type similarity | mmr (default RETRIEVAL_SEARCH_TYPE) with lambda_mult in
+    [0, 1] (MMR_LAMBDA) and fetch_k (MMR_FETCH_K, clamped to k..64): LangChain's maximal
+    marginal relevance over the first fetch_k hits of the mode, hits in pick order
     optional patient_id / from_date / to_date / include_knowledge_base scope the search to
     one patient's chunks (inside the window) plus, unless excluded, the knowledge base
 """
@@ -37,7 +40,7 @@ from fastapi import FastAPI
 from fastapi.responses import JSONResponse
 
 from ..bus.broker import get_broker
-from ..config import Settings
+from ..config import Settings, mmr_request
 from ..index import faiss_io
 from ..index.flat import FlatIndex  # noqa: F401  (the default store type)
 from ..index.hybrid import load_index, make_index
@@ -301,16 +304,22 @@ class SemanticIndexer:
 
     # ------------------------------------------------------------------ query
     @torch.inference_mode()
-    def search(self, query: str, k: int = 3, scope: dict | None = None, mode: str | None = None) -> list[dict]:
+    def search(self, query: str, k: int = 3, scope: dict | None = None, mode: str | None = None,
+               mmr: tuple | None = None) -> list[dict]:
         """``scope``: None, or a scope request (index/scope.py ``scope_request``) -- the hits
         then come from that patient / window (and the knowledge base unless excluded) only.
         ``mode``: None / ``"dense"`` (the kNN search, ``score`` = L2 distance), ``"lexical"``
         (BM25, ``score`` = BM25 score) or ``"hybrid"`` (reciprocal rank fusion of both at depth
-        ``HYBRID_FETCH_K``, ``score`` = RRF value)."""
-        # the lexical mode never uses the embedding
-        q = None if mode == "lexical" else self.encoder.encode(self.tok.encode_batch([query]))
+        ``HYBRID_FETCH_K``, ``score`` = RRF value).  ``mmr``: None or ``(lambda_mult, fetch_k)``
+        -- the k hits are re-selected for diversity (``ops.mmr_select``) out of the mode's first
+        ``fetch_k`` (clamped to k..64), in pick order, ``score`` still the mode's own."""
+        # the lexical mode uses the embedding only for the MMR relevance term
+        q = (None if mode == "lexical" and mmr is None
+             else self.encoder.encode(self.tok.encode_batch([query])))
         with self.lock:
-            if mode is not None and mode != "dense":
+            if mmr is not None:
+                D, I = self._search_mmr(q, query, k, scope, mode, mmr)
+            elif mode is not None and mode != "dense":
                 D, I = self._search_mode(q, query, k, scope, mode)
             elif scope is None:
                 D, I = self.index.search(q, k)
@@ -330,7 +339,24 @@ class SemanticIndexer:
                                 "type": m.get("type"), "doc_id": str(m.get("doc_id"))})
             return out
 
-    def _search_mode(self, q, query: str, k: int, scope, mode: str):
+    def _search_mmr(self, q, query: str, k: int, scope, mode, mmr):
+        """The mode's first ``fetch_k`` hits, then one ``mmr_select`` launch picks k of them;
+        D = the mode's score of each pick."""
+        if not 1 <= k <= 64:
+            raise ValueError("mmr search serves k in 1..64")
+        lam, fk = float(mmr[0]), min(64, max(k, int(mmr[1])))
+        if mode is not None and mode != "dense":
+            Dc, C = self._search_mode(q, query, fk, scope, mode, base_k=k)
+        elif scope is None:
+            Dc, C = self.index.search(q, fk)
+        else:
+            Dc, C = self.index.search_scoped(q, fk, self.scopes, self.scopes.scope_rows([scope]))
+        dev = C.device
+        _, I, P = self.index.mmr_select(q, C, torch.full((1,), fk, dtype=torch.int32, device=dev),
+                                        torch.full((1,), lam, dtype=torch.float32, device=dev), k)
+        return torch.gather(Dc, 1, P.clamp(min=0).long()), I
+
+    def _search_mode(self, q, query: str, k: int, scope, mode: str, base_k: int | None = None):
         from .. import ops
 
         if mode not in ("lexical", "hybrid"):
@@ -342,7 +368,8 @@ class SemanticIndexer:
         qt, qw, avgdl = lex.query_rows([query])
         if mode == "lexical":
             return self.index.search_lexical(lex, qt, qw, avgdl, k, scope_cols=cols, scope=rows)
-        depth = fetch_depth(k)
+        # under MMR k is fetch_k: the legs run at max(fetch_depth(k of the request), fetch_k)
+        depth = fetch_depth(k) if base_k is None else max(fetch_depth(base_k), k)
         _, Id = self.index.search(q, depth) if scope is None else self.index.search_scoped(q, depth, cols, rows)
         _, Il = self.index.search_lexical(lex, qt, qw, avgdl, depth, scope_cols=cols, scope=rows)
         return ops.rank_fuse(Id, Il, torch.full((1,), 2, dtype=torch.int32, device=Id.device), k)
@@ -396,9 +423,13 @@ def create_app(indexer: SemanticIndexer) -> FastAPI:
         except ValueError as e:
             return JSONResponse(status_code=422, content={"detail": str(e)})
         mode = req.search_mode or indexer.st.retrieval_mode
-        if mode != "dense":
+        try:
+            mmr = mmr_request(req.search_type, req.lambda_mult, req.fetch_k, indexer.st)
+        except ValueError as e:
+            return JSONResponse(status_code=422, content={"detail": str(e)})
+        if mode != "dense" or mmr is not None:
             try:
-                return indexer.search(req.query, req.k, scope, mode)
+                return indexer.search(req.query, req.k, scope, mode, mmr)
             except (ValueError, NotImplementedError) as e:
                 return JSONResponse(status_code=422, content={"detail": str(e)})
         if scope is None:

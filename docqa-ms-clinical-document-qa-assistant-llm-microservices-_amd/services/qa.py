@@ -8,6 +8,11 @@ Contract (llm-qa/main.py:108-126 and synthese-comparative/core/llm_client.py:42-
                             base (index/scope.py); 422 on an unparseable date
                             optional search_mode dense | lexical | hybrid (default
                             RETRIEVAL_MODE): kNN, BM25 or their rank fusion; 422 on another
+                            optional search_type similarity | mmr (default
+                            RETRIEVAL_SEARCH_TYPE), lambda_mult in [0, 1] (MMR_LAMBDA),
+                            fetch_k >= 1 (MMR_FETCH_K, clamped to k..64): LangChain's
+                            maximal marginal relevance over the first fetch_k hits; 422 on
+                            another value
                             503 {"detail": "Index non chargé."} when no index is loaded
   POST /api/llm/summarize   {"prompt"}   -> {"summary"}   (expected by synthese, missing
                             in the reference; served here)
@@ -39,7 +44,7 @@ import time
 from fastapi import FastAPI
 from fastapi.responses import JSONResponse, PlainTextResponse
 
-from ..config import Settings
+from ..config import Settings, mmr_request
 from ..engine.llm_engine import SamplingParams
 from ..index.scope import scope_request
 from ..schemas import AskResponse, Query, SummarizeRequest, SummarizeResponse
@@ -47,24 +52,26 @@ from ..utils import tracing
 from ..utils.metrics import Metrics
 
 
-def ask_payload(question: str, scope: dict | None, mode: str | None = None):
-    """The batcher payload of an ask: the plain question when it has no scope and the dense
-    retrieval mode."""
+def ask_payload(question: str, scope: dict | None, mode: str | None = None, mmr: tuple | None = None):
+    """The batcher payload of an ask: the plain question when it has no scope, the dense
+    retrieval mode and no MMR re-selection (``mmr``: None or (lambda_mult, fetch_k))."""
     if mode == "dense":
         mode = None
-    if scope is None and mode is None:
+    if scope is None and mode is None and mmr is None:
         return question
-    return {"question": question, "scope": scope, "mode": mode}
+    return {"question": question, "scope": scope, "mode": mode, "mmr": mmr}
 
 
-def _ask_parts(asks) -> tuple[list[str], list | None, list | None]:
-    """(questions, scopes, modes) of queued asks; scopes is None when no ask carries one,
-    modes is None when every ask is dense."""
+def _ask_parts(asks) -> tuple[list[str], list | None, list | None, list | None]:
+    """(questions, scopes, modes, mmr) of queued asks; scopes is None when no ask carries one,
+    modes is None when every ask is dense, mmr is None when no ask asks for MMR."""
     qs = [it[1]["question"] if isinstance(it[1], dict) else it[1] for it in asks]
     scopes = [it[1].get("scope") if isinstance(it[1], dict) else None for it in asks]
     modes = [(it[1].get("mode") if isinstance(it[1], dict) else None) or "dense" for it in asks]
+    mmr = [it[1].get("mmr") if isinstance(it[1], dict) else None for it in asks]
     return (qs, scopes if any(s is not None for s in scopes) else None,
-            modes if any(m != "dense" for m in modes) else None)
+            modes if any(m != "dense" for m in modes) else None,
+            mmr if any(m is not None for m in mmr) else None)
 
 
 def penalty_defaults(st: Settings) -> dict:
@@ -116,8 +123,10 @@ class DynamicBatcher:
         sums = [b for b in batch if b[0] == "summarize"]
         try:
             if asks:
-                qs, scopes, modes = _ask_parts(asks)
-                if modes is not None:
+                qs, scopes, modes, mmr = _ask_parts(asks)
+                if mmr is not None:
+                    res = self.pipe.answer_batch(qs, self._params(), scopes=scopes, modes=modes, mmr=mmr)
+                elif modes is not None:
                     res = self.pipe.answer_batch(qs, self._params(), scopes=scopes, modes=modes)
                 else:
                     res = (self.pipe.answer_batch(qs, self._params()) if scopes is None
@@ -301,9 +310,11 @@ class ContinuousBatcher:
         sums = [it for it in items if it[0] == "summarize"]
         if asks:
             tp0 = time.perf_counter()
-            qs, scopes, modes = _ask_parts(asks)
+            qs, scopes, modes, mmr = _ask_parts(asks)
             qemb = pipe.embed(qs)
-            if modes is not None:
+            if mmr is not None:
+                _, I = pipe.search(qemb, scopes, modes, qs, mmr)
+            elif modes is not None:
                 _, I = pipe.search(qemb, scopes, modes, qs)
             else:
                 _, I = pipe.index.search(qemb, pipe.k) if scopes is None else pipe.search(qemb, scopes)
@@ -405,7 +416,9 @@ class ReplicaRouter:
                     local = ask_payload(local, scope_request(payload.get("patient_id"), payload.get("from_date"),
                                                              payload.get("to_date"),
                                                              payload.get("include_knowledge_base", True)),
-                                        payload.get("search_mode"))
+                                        payload.get("search_mode"),
+                                        (payload["lambda_mult"], payload["fetch_k"])
+                                        if payload.get("search_type") == "mmr" else None)
                 return await asyncio.wrap_future(self.local.submit(kind, local))
             r = await self.client.post(self.targets[i] + path, json=payload)
             return JSONResponse(status_code=r.status_code, content=r.json())
@@ -445,6 +458,13 @@ def create_app(pipeline=None, settings: Settings | None = None, lockstep=None,
         mode = query.search_mode or st.retrieval_mode
         if mode not in ("dense", "lexical", "hybrid"):
             return JSONResponse(status_code=422, content={"detail": f"RETRIEVAL_MODE: unknown mode {mode!r}"})
+        try:
+            mmr = mmr_request(query.search_type, query.lambda_mult, query.fetch_k, st)
+        except ValueError as e:
+            return JSONResponse(status_code=422, content={"detail": str(e)})
+        if mmr is not None and getattr(app.state.pipeline.index, "check_gather", None) is not None:
+            return JSONResponse(status_code=422, content={"detail": "search_type mmr is not served over a "
+                                                                    "sharded index"})
         metrics.inc("ask_requests")
         if router is not None:
             payload = {"question": query.question}
@@ -453,8 +473,10 @@ def create_app(pipeline=None, settings: Settings | None = None, lockstep=None,
                                include_knowledge_base=query.include_knowledge_base)
             if mode != "dense":     # explicit, so every replica answers alike whatever its default
                 payload["search_mode"] = mode
+            if mmr is not None:     # resolved here for the same reason
+                payload.update(search_type="mmr", lambda_mult=mmr[0], fetch_k=mmr[1])
             return await router.call("ask", "/ask/", payload, "question")
-        fut = app.state.batcher.submit("ask", ask_payload(query.question, scope, mode))
+        fut = app.state.batcher.submit("ask", ask_payload(query.question, scope, mode, mmr))
         return await asyncio.wrap_future(fut)
 
     @app.post("/api/llm/summarize", response_model=SummarizeResponse)
