@@ -2029,6 +2029,97 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> mmr_select(const at::Tensor& xb, 
   return {out_s, out_i, out_p};
 }
 
+// row compaction for deletes (compact.hip).  keep uint8 [n], w int64 [n] or none -> pos int64
+// [n+1], the exclusive prefix sum of keep[r] ? w[r] : 0
+static void check_keep(const at::Tensor& keep, const char* what) {
+  TORCH_CHECK(keep.is_cuda() && keep.is_contiguous() && keep.dim() == 1 && keep.scalar_type() == at::kByte, what,
+              ": keep must be a contiguous uint8 [n] GPU tensor");
+}
+static void check_pos(const at::Tensor& pos, int64_t n, const char* what) {
+  TORCH_CHECK(pos.is_cuda() && pos.is_contiguous() && pos.scalar_type() == at::kLong && pos.numel() == n + 1, what,
+              ": pos must be a contiguous int64 [n + 1] GPU tensor");
+}
+
+at::Tensor masked_scan(const at::Tensor& keep, const c10::optional<at::Tensor>& w) {
+  check_keep(keep, "masked_scan");
+  const int64_t n = keep.numel();
+  const int64_t* wp = nullptr;
+  if (w.has_value()) {
+    TORCH_CHECK(w->is_cuda() && w->is_contiguous() && w->scalar_type() == at::kLong && w->numel() == n,
+                "masked_scan: w must be a contiguous int64 [n] GPU tensor");
+    wp = w->data_ptr<int64_t>();
+  }
+  c10::DeviceGuard g(keep.device());
+  auto opt = keep.options().dtype(at::kLong);
+  auto pos = at::empty({n + 1}, opt);
+  auto ws = at::empty({docqa_masked_scan_workspace(n)}, opt);
+  CHECK_RC(docqa_masked_scan(keep.data_ptr<uint8_t>(), wp, n, pos.data_ptr<int64_t>(), ws.data_ptr<int64_t>(),
+                             stream()), "masked_scan");
+  return pos;
+}
+
+// out[pos[r]] = src[r] for kept rows; src [n, ...] and out [n_out, ...] of one dtype and row shape
+void gather_rows(const at::Tensor& src, const at::Tensor& keep, const at::Tensor& pos, at::Tensor out) {
+  CHECK_GPU(src); CHECK_GPU(out); CHECK_CONTIG(src); CHECK_CONTIG(out);
+  check_keep(keep, "gather_rows");
+  TORCH_CHECK(src.dim() >= 1 && out.dim() == src.dim() && src.scalar_type() == out.scalar_type(),
+              "gather_rows: src and out must have one dtype and rank");
+  const int64_t n = src.size(0);
+  TORCH_CHECK(keep.numel() == n, "gather_rows: keep must be [n]");
+  check_pos(pos, n, "gather_rows");
+  for (int64_t i = 1; i < src.dim(); ++i)
+    TORCH_CHECK(src.size(i) == out.size(i), "gather_rows: src and out rows differ");
+  const int64_t W = (n > 0 ? src.numel() / n : (out.size(0) > 0 ? out.numel() / out.size(0) : 1)) *
+                    (int64_t)src.element_size();
+  if (n == 0 || out.size(0) == 0) return;
+  TORCH_CHECK(W >= 1, "gather_rows: empty rows");
+  const char* a = static_cast<const char*>(src.data_ptr());
+  const char* b = static_cast<const char*>(out.data_ptr());
+  TORCH_CHECK(a + src.numel() * src.element_size() <= b || b + out.numel() * out.element_size() <= a,
+              "gather_rows: out must not alias src");
+  c10::DeviceGuard g(src.device());
+  CHECK_RC(docqa_gather_rows(src.data_ptr(), out.data_ptr(), keep.data_ptr<uint8_t>(), pos.data_ptr<int64_t>(), n,
+                             W, out.size(0), stream()), "gather_rows");
+}
+
+// CSR rows: -> (row_ptr' int64 [n_out + 1], terms' int32 [e_out], tfs' uint8 [e_out])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> csr_gather(const at::Tensor& row_ptr, const at::Tensor& keep,
+                                                          const at::Tensor& pos, const at::Tensor& epos,
+                                                          const at::Tensor& terms, const at::Tensor& tfs,
+                                                          int64_t n_out, int64_t e_out) {
+  check_keep(keep, "csr_gather");
+  const int64_t n = keep.numel();
+  check_pos(pos, n, "csr_gather"); check_pos(epos, n, "csr_gather"); check_pos(row_ptr, n, "csr_gather");
+  CHECK_GPU(terms); CHECK_GPU(tfs); CHECK_CONTIG(terms); CHECK_CONTIG(tfs); CHECK_I32(terms);
+  TORCH_CHECK(tfs.scalar_type() == at::kByte && tfs.numel() == terms.numel() && terms.dim() == 1,
+              "csr_gather: terms int32 [E], tfs uint8 [E]");
+  TORCH_CHECK(n_out >= 0 && n_out <= n && e_out >= 0 && e_out <= terms.numel(), "csr_gather: n_out / e_out");
+  c10::DeviceGuard g(keep.device());
+  auto new_ptr = at::zeros({n_out + 1}, row_ptr.options());
+  auto new_terms = at::empty({e_out}, terms.options());
+  auto new_tfs = at::empty({e_out}, tfs.options());
+  CHECK_RC(docqa_csr_gather(row_ptr.data_ptr<int64_t>(), keep.data_ptr<uint8_t>(), pos.data_ptr<int64_t>(),
+                            epos.data_ptr<int64_t>(), n, terms.data_ptr<int>(), tfs.data_ptr<uint8_t>(),
+                            terms.numel(), new_ptr.data_ptr<int64_t>(), n_out + 1, new_terms.data_ptr<int>(),
+                            new_tfs.data_ptr<uint8_t>(), e_out, stream()), "csr_gather");
+  return {new_ptr, new_terms, new_tfs};
+}
+
+// ids'[j] = pos[ids[j]]
+at::Tensor remap_ids(const at::Tensor& ids, const at::Tensor& pos) {
+  CHECK_GPU(ids); CHECK_CONTIG(ids); CHECK_GPU(pos); CHECK_CONTIG(pos);
+  TORCH_CHECK(ids.scalar_type() == at::kLong && pos.scalar_type() == at::kLong && pos.numel() >= 1,
+              "remap_ids: ids int64, pos int64 [n + 1]");
+  c10::DeviceGuard g(ids.device());
+  auto out = at::empty_like(ids);
+  CHECK_RC(docqa_remap_ids(ids.data_ptr<int64_t>(), ids.numel(), pos.data_ptr<int64_t>(), pos.numel() - 1,
+                           out.data_ptr<int64_t>(), stream()), "remap_ids");
+  return out;
+}
+
+int64_t compact_scan_tile() { return docqa_compact_scan_tile(); }
+int64_t compact_scan_levels() { return docqa_compact_scan_levels(); }
+
 // IVF coarse quantizer, wide probes: int64 [nq, nprobe] nearest centroids (ascending, ties
 // to the lower id) for nprobe <= 512
 // exact fp32 x @ w^T on the coarse quantizer's MFMA tiles (the IVF-PQ query pre-rotation)
@@ -2303,6 +2394,13 @@ TORCH_LIBRARY(docqa, m) {
   m.def("rank_fuse(Tensor i_dense, Tensor i_lex, Tensor mode, int k, int c) -> (Tensor, Tensor)");
   m.def("mmr_select(Tensor xb, Tensor xb_norms, Tensor xq, Tensor cand, Tensor ncand, Tensor lam, int k) "
         "-> (Tensor, Tensor, Tensor)");
+  m.def("masked_scan(Tensor keep, Tensor? w) -> Tensor");
+  m.def("gather_rows(Tensor src, Tensor keep, Tensor pos, Tensor(a!) out) -> ()");
+  m.def("csr_gather(Tensor row_ptr, Tensor keep, Tensor pos, Tensor epos, Tensor terms, Tensor tfs, int n_out, "
+        "int e_out) -> (Tensor, Tensor, Tensor)");
+  m.def("remap_ids(Tensor ids, Tensor pos) -> Tensor");
+  m.def("compact_scan_tile() -> int", &compact_scan_tile);
+  m.def("compact_scan_levels() -> int", &compact_scan_levels);
   m.def("coarse_probes(Tensor xq, Tensor cent, Tensor cnorm, int nprobe) -> Tensor");
   m.def("fp32_gemm_nt(Tensor x, Tensor w) -> Tensor");
   m.def("ivfpq_search(Tensor xq, Tensor centroids, Tensor pq, Tensor codes, Tensor ids, "
@@ -2424,6 +2522,10 @@ TORCH_LIBRARY_IMPL(docqa, CUDA, m) {
   m.impl("bm25_topk", &bm25_topk);
   m.impl("rank_fuse", &rank_fuse);
   m.impl("mmr_select", &mmr_select);
+  m.impl("masked_scan", &masked_scan);
+  m.impl("gather_rows", &gather_rows);
+  m.impl("csr_gather", &csr_gather);
+  m.impl("remap_ids", &remap_ids);
   m.impl("pool_l2", &pool_l2);
   m.impl("ivfpq_search", &ivfpq_search);
   m.impl("ivfpq_search_pt", &ivfpq_search_pt);

@@ -320,6 +320,27 @@ int docqa_mmr_select(const void* xb, const float* norms, int64_t N, int d, int i
                      const int64_t* cand, int F, const int* ncand, const float* lam, int nq, int k,
                      float* out_s, int64_t* out_i, int* out_p, hipStream_t s);
 
+// row compaction for deletes (compact.hip): exact and deterministic, int64 index arithmetic, no
+// workgroup waits on another.  masked scan: pos int64 [n+1] = exclusive prefix sum of
+// keep[r] ? w[r] : 0 (w null: 1), ws = docqa_masked_scan_workspace(n) int64 words; -1 above
+// docqa_compact_scan_tile()^docqa_compact_scan_levels() rows
+int docqa_compact_scan_tile();
+int docqa_compact_scan_levels();
+int64_t docqa_masked_scan_workspace(int64_t n);
+int docqa_masked_scan(const uint8_t* keep, const int64_t* w, int64_t n, int64_t* pos, int64_t* ws,
+                      hipStream_t s);
+// dst[pos[r]] = src[r] for kept rows of W bytes (16-byte, 4-byte or byte lanes by alignment); dst
+// holds dst_rows rows and never aliases src; positions outside dst are not written
+int docqa_gather_rows(const void* src, void* dst, const uint8_t* keep, const int64_t* pos, int64_t n,
+                      int64_t W, int64_t dst_rows, hipStream_t s);
+// CSR rows: pos the row scan, epos the scan weighted by row length; new_ptr [ptr_rows], the
+// entries of kept rows (terms and / or tfs, either may be null) copied in order into e_cap slots
+int docqa_csr_gather(const int64_t* row_ptr, const uint8_t* keep, const int64_t* pos, const int64_t* epos,
+                     int64_t n, const int* terms, const uint8_t* tfs, int64_t e_in, int64_t* new_ptr,
+                     int64_t ptr_rows, int* new_terms, uint8_t* new_tfs, int64_t e_cap, hipStream_t s);
+// out[j] = pos[ids[j]] (ids outside [0, n): -1)
+int docqa_remap_ids(const int64_t* ids, int64_t m, const int64_t* pos, int64_t n, int64_t* out, hipStream_t s);
+
 int docqa_ivfpq_search(const float* xq, const float* centroids, const float* pq,
                        const uint8_t* codes, const int64_t* ids, const int64_t* list_off,
                        const int64_t* probes, int nq, int nprobe, int d, int M, int k,

@@ -23,6 +23,19 @@ from .. import ops
 from . import faiss_io
 
 
+def removal_mask(ids, n: int, device):
+    """(``keep`` uint8 [n], ``pos`` int64 [n+1], removed) for deleting the row ids ``ids`` from
+    ``n`` rows: ids outside ``[0, n)`` and duplicates are ignored (FAISS ``remove_ids``), ``pos``
+    is ``ops.masked_scan(keep)`` -- the new position of every surviving row.  The count comes
+    from the host-side id list, so nothing here waits for the device."""
+    host = np.unique(np.asarray(torch.as_tensor(ids).cpu(), dtype=np.int64).reshape(-1))
+    host = host[(host >= 0) & (host < n)]
+    keep = torch.ones(n, dtype=torch.uint8, device=device)
+    if host.size:
+        keep[torch.from_numpy(host).to(device)] = 0
+    return keep, ops.masked_scan(keep), int(host.size)
+
+
 class FlatIndex:
     def __init__(self, d: int, metric: str = "l2", device="cuda", storage_dtype=torch.float32,
                  capacity: int = 1024):
@@ -68,11 +81,12 @@ class FlatIndex:
         with self._lock:
             self.ntotal = 0
 
-    def replace(self, x, before_swap=None) -> None:
+    def replace(self, x, before_swap=None, after_swap=None) -> None:
         """Replace the whole content with ``x`` [n, d] without an empty or partial
         intermediate state: the new storage is built off to the side, then swapped in
         under the lock (``before_swap()``, e.g. a metadata swap, runs under the same
-        lock), so a concurrent search sees either the old or the new index."""
+        lock, ``after_swap()`` as its last statement), so a concurrent search sees either the
+        old or the new index."""
         x = torch.as_tensor(x)
         if x.dim() == 1:
             x = x[None]
@@ -92,6 +106,46 @@ class FlatIndex:
             if before_swap is not None:
                 before_swap()
             self._xb, self._norms, self.ntotal = xb, nm, n
+            if after_swap is not None:
+                after_swap()
+
+    def remove_ids(self, ids, before_swap=None, after_swap=None, mask=None) -> int:
+        """Remove the rows ``ids`` (FAISS ``IndexFlat::remove_ids``): surviving rows keep their
+        order and later ids shift down; ids outside ``[0, ntotal)`` and duplicates are ignored.
+        Returns the number of rows removed (0: nothing changes, ``before_swap`` is not called).
+
+        Same discipline as :meth:`replace`: the compacted vectors and norms are built off to
+        the side (``ops.gather_rows``, out of place), the stream is synchronised, then they are
+        swapped in under the lock with ``before_swap()`` -- the metadata and column swap --
+        running under the same lock.  A search in flight on another stream keeps reading the old
+        buffers (``search`` recorded its stream on them).  Transient memory: one extra copy of
+        the store (the surviving rows) until the old buffers are released.  ``after_swap()``
+        runs as the last statement under the lock, once the new buffers are in place.  ``mask``:
+        the ``removal_mask(ids, ntotal, device)`` a caller already made for its own columns."""
+        with self._lock:
+            n, xb, nm = self.ntotal, self._xb, self._norms
+        keep, pos, removed = mask if mask is not None else removal_mask(ids, n, self.device)
+        if keep.numel() != n:
+            raise ValueError(f"remove_ids: the mask covers {keep.numel()} rows, the index holds {n}")
+        if removed == 0:
+            return 0
+        left = n - removed
+        cap = max(1024, left)
+        new_xb = torch.empty(cap, self.d, device=self.device, dtype=self.storage_dtype)
+        new_nm = torch.empty(cap, device=self.device, dtype=torch.float32)
+        ops.gather_rows(xb[:n], keep, pos, out=new_xb)
+        ops.gather_rows(nm[:n], keep, pos, out=new_nm)
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
+        with self._lock:
+            if self.ntotal != n or self._xb is not xb:
+                raise RuntimeError("remove_ids: the index changed during the delete (writers must be serialised)")
+            if before_swap is not None:
+                before_swap()
+            self._xb, self._norms, self.ntotal = new_xb, new_nm, left
+            if after_swap is not None:
+                after_swap()
+        return removed
 
     # ------------------------------------------------------------------ query
     @property
@@ -129,7 +183,9 @@ class FlatIndex:
         xq = xq.to(self.device, dtype=torch.float32)
         scope = torch.as_tensor(scope).to(self.device, dtype=torch.int32)
         with self._lock:
-            n = min(self.ntotal, cols.n)      # before the buffers: they only ever grow
+            # a delete swaps vectors and columns together under this lock, an add extends the
+            # columns first: min() is a row count every buffer read below covers
+            n = min(self.ntotal, cols.n)
             xb, nm, tags, days = self._xb, self._norms, cols._tags, cols._days
             if xb.is_cuda:
                 # as in search(): the kernel may run on a side stream while these are dropped
@@ -147,7 +203,7 @@ class FlatIndex:
         matching rows.  Exact (the columns do not depend on the vectors); covers rows
         ``[0, min(ntotal, cols.n[, scope_cols.n]))``."""
         with self._lock:
-            n = min(self.ntotal, cols.n)      # before the buffers: they only ever grow
+            n = min(self.ntotal, cols.n)      # as in search_scoped()
             if scope is not None:
                 n = min(n, scope_cols.n)
             bufs = [cols._row_ptr, cols._terms, cols._tfs, cols._dl]

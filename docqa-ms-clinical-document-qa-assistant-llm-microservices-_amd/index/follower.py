@@ -22,9 +22,9 @@ from pathlib import Path
 import torch
 
 from ..store import metadata_io
-from ..store.segment_log import read_snapshot_marker, tail_frames
+from ..store.segment_log import DeleteFrame, read_snapshot_marker, tail_frames
 from . import faiss_io
-from .flat import FlatIndex
+from .flat import FlatIndex, removal_mask
 from .lexical import LexicalColumns
 from .scope import ScopeColumns
 
@@ -62,6 +62,9 @@ class IndexFollower:
         self._stop = threading.Event()
         self._thread: threading.Thread | None = None
         self.version = 0
+        # a delete shifts row ids: odd while one is swapping the (index, metadata) pair, even
+        # otherwise (see SemanticIndexer.generation); a snapshot reload bumps it by two
+        self.generation = 0
 
     # ------------------------------------------------------------------ load / tail
     def _load_snapshot(self) -> None:
@@ -86,23 +89,32 @@ class IndexFollower:
         xb = torch.from_numpy(data.xb) if n else torch.empty(0, self.index.d)
 
         def swap_meta():
+            self.generation += 1
             with self._lex_lock:     # ensure_lexical() never reads a half-swapped list
                 self.metadata[:] = meta
                 if self.lexical is not None:
                     self.lexical.rebuild(self.metadata)
             self.scopes.rebuild(self.metadata)
 
-        if ivf is not None and hasattr(self.index, "ivf"):
-            self.index.replace(xb, before_swap=swap_meta, ivf=ivf)
-        else:
-            self.index.replace(xb, before_swap=swap_meta)
+        def swapped():                       # last statement under the index lock
+            self.generation += 1
+
+        try:
+            if ivf is not None and hasattr(self.index, "ivf"):
+                self.index.replace(xb, before_swap=swap_meta, ivf=ivf, after_swap=swapped)
+            else:
+                self.index.replace(xb, before_swap=swap_meta, after_swap=swapped)
+        finally:
+            if self.generation & 1:          # the swap itself failed half-way
+                self.generation += 1
         self._marker = mk
         self.last_seq = mk["wal_seq"]
         self._offset = 0
         self.version += 1
 
     def poll(self) -> int:
-        """Apply what the writer made durable since the last call; returns rows added."""
+        """Apply what the writer made durable since the last call, adds and deletes in log
+        order; returns rows added."""
         if self._marker is None or read_snapshot_marker(self.marker_path) != self._marker:
             self._load_snapshot()            # first load, or the writer took a snapshot
         try:   # the writer rotates the log by replacing the file: restart at its head
@@ -112,9 +124,14 @@ class IndexFollower:
         except FileNotFoundError:
             self._offset = 0
         frames, self._offset = tail_frames(self.wal_path, self._offset)
-        added = 0
+        added, changed = 0, False
         for seq, recs, vecs in frames:
             if seq <= self.last_seq:
+                continue
+            if isinstance(recs, DeleteFrame):
+                self._apply_delete(recs)
+                self.last_seq = seq
+                changed = True
                 continue
             self.metadata.extend(recs)       # records first: every searchable id resolves
             self.scopes.extend(self.metadata)
@@ -124,9 +141,39 @@ class IndexFollower:
             self.index.add(torch.from_numpy(vecs.copy()))
             self.last_seq = seq
             added += len(recs)
-        if added:
+        if added or changed:
             self.version += 1
         return added
+
+    def _apply_delete(self, frame: DeleteFrame) -> None:
+        """Vectors, metadata and columns leave together under the index lock."""
+        rows, n = frame["rows"], self.index.ntotal
+        if frame["ntotal_before"] != n or len(self.metadata) != n:
+            raise RuntimeError(f"delete frame expects {frame['ntotal_before']} rows, the replica holds {n}")
+        keep, pos, removed = removal_mask(rows, n, self.index.device)
+        gone = [self.metadata[i] for i in rows]
+
+        def swap():
+            # what can fail (checks, new device buffers) first, changing nothing; then the bump,
+            # the list surgery and the reference swaps
+            with self._lex_lock:
+                commit_scopes = self.scopes.prepare_remove(keep, pos, n - removed)
+                commit_lexical = (self.lexical.prepare_remove(keep, pos, n - removed, gone)
+                                  if self.lexical is not None else None)
+                self.generation += 1
+                metadata_io.drop_rows(self.metadata, rows)
+                if commit_lexical is not None:
+                    commit_lexical()
+            commit_scopes()
+
+        def swapped():                       # last statement under the index lock
+            self.generation += 1
+
+        try:
+            self.index.remove_ids(rows, before_swap=swap, after_swap=swapped, mask=(keep, pos, removed))
+        finally:
+            if self.generation & 1:
+                self.generation += 1
 
     def ensure_lexical(self) -> LexicalColumns:
         """The BM25 term columns of the metadata list, built on the first call."""

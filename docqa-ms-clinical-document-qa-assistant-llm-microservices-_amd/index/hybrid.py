@@ -98,7 +98,7 @@ class IVFPQRefineIndex:
             self.flat.reset()
             self.ivf = None
 
-    def replace(self, x, before_swap=None, ivf: IVFPQIndex | None = None) -> None:
+    def replace(self, x, before_swap=None, ivf: IVFPQIndex | None = None, after_swap=None) -> None:
         """Whole-content swap (index follower): the new exact vectors and (if given) an
         already-trained IVF-PQ over them, else retrain when the store is big enough."""
         with self._lock:
@@ -106,6 +106,46 @@ class IVFPQRefineIndex:
             self.ivf = ivf.to(self.device) if ivf is not None else None
             if self.ivf is None and self.flat.ntotal >= self.train_min:
                 self._train()
+            if after_swap is not None:
+                after_swap()
+
+    def remove_ids(self, ids, before_swap=None, after_swap=None, mask=None) -> int:
+        """Remove rows from the exact store (:meth:`FlatIndex.remove_ids`) and, once trained,
+        from the inverted lists: the list-position mask is ``keep[ivf.ids]``; ``codes``, ``ids``
+        and ``norms`` are gathered with it, the surviving ids are mapped to their new rows, and
+        the new list offsets are the list-position scan read at the old offsets.  The quantizers
+        stay as trained, also when ``ntotal`` falls below ``train_min``."""
+        from .. import ops
+        from .flat import removal_mask
+
+        with self._lock:
+            ivf = self.ivf
+            if ivf is None:
+                return self.flat.remove_ids(ids, before_swap=before_swap, after_swap=after_swap, mask=mask)
+            n = self.flat.ntotal
+            keep, pos, removed = mask if mask is not None else removal_mask(ids, n, self.device)
+            if removed == 0:
+                return 0
+            if ivf.ntotal != n or ivf.ids.shape[0] != n:
+                raise RuntimeError(f"inverted lists hold {ivf.ids.shape[0]} rows, the flat store {n}")
+            lkeep = keep[ivf.ids]                             # uint8 per list position
+            lpos = ops.masked_scan(lkeep)
+            left = n - removed
+            codes = ops.gather_rows(ivf.codes, lkeep, lpos, left)
+            new_ids = ops.remap_ids(ops.gather_rows(ivf.ids, lkeep, lpos, left), pos)
+            norms = ivf.norms
+            if norms is not None and norms.shape[0] == n:
+                norms = ops.gather_rows(norms.contiguous(), lkeep, lpos, left)
+            else:
+                norms = None                                  # rebuilt from the codes on the next search
+            list_off = lpos[ivf.list_off]
+
+            def swap():
+                if before_swap is not None:
+                    before_swap()
+                ivf.codes, ivf.ids, ivf.norms, ivf.list_off, ivf.ntotal = codes, new_ids, norms, list_off, left
+
+            return self.flat.remove_ids(ids, before_swap=swap, after_swap=after_swap, mask=(keep, pos, removed))
 
     # ------------------------------------------------------------------ query
     def search(self, xq, k: int, id_offset: int = 0, nprobe: int | None = None):

@@ -138,6 +138,62 @@ class LexicalColumns:
         self.df, self.total_len, self.entries, self.n = {}, 0, 0, 0
         self.extend(metadata)
 
+    @torch.inference_mode(False)
+    def remove(self, keep: torch.Tensor, pos: torch.Tensor, n_out: int, removed: list[dict]) -> None:
+        self.prepare_remove(keep, pos, n_out, removed)()
+
+    @torch.inference_mode(False)
+    def prepare_remove(self, keep: torch.Tensor, pos: torch.Tensor, n_out: int, removed: list[dict]):
+        """Two-step :meth:`remove`: the validation and every new device buffer are made here and
+        change nothing; the returned ``commit()`` only swaps references and updates statistics.
+
+        Drop the rows a delete removes: ``keep`` uint8 [n], ``pos`` its ``ops.masked_scan``,
+        ``n_out`` the surviving count, ``removed`` the removed rows' records (their text is
+        analysed again for the statistics: ``df`` is decremented and a term that reaches 0 is
+        dropped, ``total_len`` and ``entries`` shrink by what the rows held -- so no count is
+        read back from the device).  Same rule as :meth:`extend`: the new buffers are complete
+        on the device before they and ``n`` become visible."""
+        from .. import ops
+
+        if keep.numel() != self.n or self.n - n_out != len(removed):
+            raise ValueError(f"lexical columns cover {self.n} rows: mask {keep.numel()}, {n_out} left, "
+                             f"{len(removed)} records")
+        df_sub: dict[int, int] = {}
+        gone_entries = gone_len = 0
+        for m in removed:
+            pairs, dl = analyze_full(m.get("text_content", "") or "")
+            for h, _ in pairs:
+                df_sub[h] = df_sub.get(h, 0) + 1
+            gone_entries += len(pairs)
+            gone_len += dl
+        e_out = self.entries - gone_entries
+        if e_out < 0 or any(self.df.get(h, 0) < c for h, c in df_sub.items()):
+            raise ValueError("lexical columns: the removed records do not match the rows they name")
+        row_ptr = self._row_ptr[: self.n + 1]
+        epos = ops.masked_scan(keep, row_ptr[1:] - row_ptr[:-1])
+        new_ptr, terms, tfs = ops.csr_gather(row_ptr, keep, pos, epos, self._terms[: self.entries],
+                                             self._tfs[: self.entries], n_out, e_out)
+        dl_t = ops.gather_rows(self._dl[: self.n], keep, pos, n_out)
+        if e_out == 0:       # the scan kernel is never handed an empty buffer
+            terms, tfs = self._grown(terms, 0, 1), self._grown(tfs, 0, 1)
+        if n_out == 0:
+            new_ptr, dl_t = self._grown(new_ptr, 1, 2), self._grown(dl_t, 0, 1)
+        self._sync()
+
+        def commit() -> None:
+            self._row_ptr, self._dl, self._terms, self._tfs = new_ptr, dl_t, terms, tfs
+            for h, c in df_sub.items():
+                left = self.df[h] - c
+                if left:
+                    self.df[h] = left
+                else:
+                    del self.df[h]
+            self.total_len -= gone_len
+            self.entries = e_out
+            self.n = n_out
+
+        return commit
+
     # ------------------------------------------------------------------ queries
     @property
     def avgdl(self) -> float:

@@ -141,6 +141,33 @@ class ScopeColumns:
         self._tag_of, self.n = {}, 0
         self.extend(metadata)
 
+    def remove(self, keep: torch.Tensor, pos: torch.Tensor, n_out: int) -> None:
+        self.prepare_remove(keep, pos, n_out)()
+
+    def prepare_remove(self, keep: torch.Tensor, pos: torch.Tensor, n_out: int):
+        """Two-step :meth:`remove`: everything that can fail (the check, the device buffers) happens
+        here and changes nothing; the returned ``commit()`` only swaps references.
+
+        Drop the rows a delete removes: ``keep`` uint8 [n], ``pos`` its ``ops.masked_scan``,
+        ``n_out`` the surviving count (``index.flat.removal_mask``).  New buffers, complete on
+        the device before they become visible; ``_tag_of`` stays as it is (a patient whose rows
+        are all gone keeps a tag that no row carries)."""
+        from .. import ops
+
+        if keep.numel() != self.n:
+            raise ValueError(f"scope columns cover {self.n} rows, the mask {keep.numel()}")
+        cap = max(1024, n_out)
+        tags = torch.zeros(cap, dtype=torch.int32, device=self.device)
+        days = torch.zeros(cap, dtype=torch.int32, device=self.device)
+        ops.gather_rows(self._tags[: self.n], keep, pos, out=tags)
+        ops.gather_rows(self._days[: self.n], keep, pos, out=days)
+        self._sync()
+
+        def commit() -> None:
+            self._tags, self._days, self.n = tags, days, n_out
+
+        return commit
+
     # ------------------------------------------------------------------ queries
     def scope_row(self, req) -> tuple[int, int, int, int]:
         if req is None:

@@ -224,6 +224,13 @@ class ShardedIndex:
             "Document frequencies and the average length would have to agree across ranks, and "
             "no service builds a sharded index. That belongs with sharding the deployed index.")
 
+    can_remove = False      # writers ask before they log a delete
+
+    def remove_ids(self, ids, before_swap=None, after_swap=None, mask=None) -> int:
+        raise NotImplementedError(
+            "A delete shifts the ids of every later row on every rank, and no service builds a "
+            "sharded index. That belongs with sharding the deployed index.")
+
     def mmr_select(self, xq, cand, ncand, lam, k: int):
         raise NotImplementedError(
             "The candidates' vectors live on the ranks that hold their rows, and no service builds "

@@ -2000,6 +2000,76 @@ def mmr_select(xb, xb_norms, xq, cand, ncand, lam, k: int):
     return ref.mmr_select(xb, xb_norms, xq, cand, ncand, lam, k)
 
 
+# ----------------------------------------------------------------------------- row compaction
+# Deleting rows from the store (csrc/kernels/compact.hip): a masked scan gives every surviving
+# row its new position, then each per-row column is gathered out of place.  Exact and
+# deterministic; no host sync.  The scan is reduce-then-scan over tiles of SCAN_TILE values with
+# SCAN_LEVELS levels at most, so the kernel serves up to SCAN_TILE ** SCAN_LEVELS rows (the
+# values csrc/kernels/compact.hip is built with: kScanTile, docqa_compact_scan_levels).
+SCAN_TILE = 1024
+SCAN_LEVELS = 3
+GATHER_MAX_ROW_BYTES = 1 << 20
+
+
+def _compact_native(t: torch.Tensor) -> bool:
+    return _gpu(t) and os.environ.get("DOCQA_COMPACT", "1") != "0"
+
+
+def masked_scan(keep, w=None):
+    """``keep`` uint8 [n] (non-zero = the row survives), ``w`` int64 [n] or None -> ``pos`` int64
+    [n+1]: the exclusive prefix sum of ``keep[r] ? w[r] : 0`` (``w`` = 1 without weights), so
+    ``pos[r]`` is row r's new position and ``pos[n]`` the surviving total.  GPU: 1 / 3 / 5
+    launches by size (per-tile sums, scan of the sums, per-tile finalisation; no workgroup waits
+    on another).  CPU tensors, ``DOCQA_COMPACT=0`` (kill switch) and anything outside the
+    envelope (uint8 mask, int64 weights, n <= SCAN_TILE ** SCAN_LEVELS) take
+    ``reference.masked_scan`` on the same device."""
+    n = keep.numel()
+    if (_compact_native(keep) and keep.dtype == torch.uint8 and keep.dim() == 1 and n <= SCAN_TILE ** SCAN_LEVELS
+            and (w is None or (w.dtype == torch.int64 and w.shape == keep.shape and w.device == keep.device))):
+        return _native().masked_scan(keep.contiguous(), None if w is None else w.contiguous())
+    return ref.masked_scan(keep, w)
+
+
+def gather_rows(src, keep, pos, n_out: int | None = None, out=None):
+    """Compact the kept rows of ``src`` [n, ...] (any dtype; rows of W bytes): ``out[pos[r]] =
+    src[r]``.  ``out`` (given, or ``torch.empty`` of ``n_out`` rows) is a different buffer from
+    ``src`` with at least ``pos[n]`` rows; rows past that are left as they are.  GPU: one
+    streaming launch on 16-byte lanes when W and both bases allow, else 4-byte lanes, else bytes.
+    Returns ``out``.  The reference runs for CPU tensors, ``DOCQA_COMPACT=0``, rows wider than
+    ``GATHER_MAX_ROW_BYTES`` and non-contiguous operands."""
+    if out is None:
+        out = torch.empty((int(n_out),) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    n = src.shape[0]
+    W = (src.numel() // n if n else 1) * src.element_size()
+    if (_compact_native(src) and keep.dtype == torch.uint8 and pos.dtype == torch.int64 and src.is_contiguous()
+            and out.is_contiguous() and keep.is_contiguous() and pos.is_contiguous() and 1 <= W <= GATHER_MAX_ROW_BYTES
+            and out.dtype == src.dtype and out.shape[1:] == src.shape[1:] and pos.numel() == n + 1):
+        _native().gather_rows(src, keep, pos, out)
+        return out
+    return ref.gather_rows(src, keep, pos, out)
+
+
+def csr_gather(row_ptr, keep, pos, epos, terms, tfs, n_out: int, e_out: int):
+    """The kept rows of a CSR: ``row_ptr`` int64 [n+1], ``pos`` the row scan, ``epos`` the scan
+    weighted by the row lengths, ``terms`` int32 / ``tfs`` uint8 [>= row_ptr[n]] -> (``row_ptr'``
+    int64 [n_out+1], ``terms'`` [e_out], ``tfs'`` [e_out]), one launch.  ``n_out`` / ``e_out``
+    are ``pos[n]`` / ``epos[n]``, which the caller knows on the host (no sync here)."""
+    if (_compact_native(row_ptr) and keep.dtype == torch.uint8 and terms.dtype == torch.int32
+            and tfs.dtype == torch.uint8 and terms.numel() == tfs.numel() and 0 <= n_out <= keep.numel()
+            and 0 <= e_out <= terms.numel()):
+        return tuple(_native().csr_gather(row_ptr.contiguous(), keep.contiguous(), pos.contiguous(),
+                                          epos.contiguous(), terms.contiguous(), tfs.contiguous(), n_out, e_out))
+    return ref.csr_gather(row_ptr, keep, pos, epos, terms, tfs, n_out, e_out)
+
+
+def remap_ids(ids, pos):
+    """``ids'[j] = pos[ids[j]]`` over a list of row ids that survived (the IVF lists name rows of
+    the flat store); an id outside ``[0, n)`` becomes -1."""
+    if _compact_native(ids) and ids.dtype == torch.int64 and pos.dtype == torch.int64 and pos.numel() >= 1:
+        return _native().remap_ids(ids.contiguous(), pos.contiguous())
+    return ref.remap_ids(ids, pos)
+
+
 def fp32_matmul_nt(x, w):
     """Exact fp32 ``x @ w.T`` on the coarse quantizer's MFMA tiles (coarse.hip) -- the IVF-PQ
     query pre-rotation on the GPU without a library GEMM; torch on the CPU."""

@@ -1015,3 +1015,40 @@ def schema_advance(sstate, nxt, tok_off, tok_bytes, pool, eos_id: int, valid=Non
             st, ws = e & J.NEXT_MASK, (ws + 1 if e & J.WS_FLAG else 0)
         if st >= 0:
             sstate[r] = J.pack(st, ws, slot)
+
+
+# ----------------------------------------------------------------------------- row compaction
+def masked_scan(keep, w=None):
+    """pos int64 [n+1]: exclusive prefix sum of ``keep[r] ? w[r] : 0`` (``w`` = 1 when None);
+    ``pos[n]`` is the surviving total."""
+    k = keep.reshape(-1) != 0
+    v = k.to(torch.int64) if w is None else torch.where(k, w.reshape(-1).to(torch.int64), 0)
+    pos = torch.zeros(k.numel() + 1, dtype=torch.int64, device=keep.device)
+    if k.numel():
+        pos[1:] = torch.cumsum(v, 0)
+    return pos
+
+
+def gather_rows(src, keep, pos, out):
+    """``out[pos[r]] = src[r]`` for kept rows (boolean indexing: surviving rows keep their
+    order); ``pos`` is only used for the count it implies."""
+    rows = src[keep.reshape(-1) != 0]
+    out[: rows.shape[0]] = rows[: out.shape[0]]
+    return out
+
+
+def csr_gather(row_ptr, keep, pos, epos, terms, tfs, n_out: int, e_out: int):
+    """(row_ptr', terms', tfs') of the kept rows of a CSR."""
+    k = keep.reshape(-1) != 0
+    lens = row_ptr[1:] - row_ptr[:-1]
+    new_ptr = torch.zeros(n_out + 1, dtype=torch.int64, device=row_ptr.device)
+    new_ptr[1:] = torch.cumsum(lens[k], 0)[:n_out]
+    emask = torch.repeat_interleave(k, lens)
+    return new_ptr, terms[: emask.numel()][emask][:e_out].clone(), tfs[: emask.numel()][emask][:e_out].clone()
+
+
+def remap_ids(ids, pos):
+    """``pos[ids]``; ids outside ``[0, n)`` become -1."""
+    n = pos.numel() - 1
+    ok = (ids >= 0) & (ids < n)
+    return torch.where(ok, pos[ids.clamp(0, max(n - 1, 0))], torch.full_like(ids, -1))

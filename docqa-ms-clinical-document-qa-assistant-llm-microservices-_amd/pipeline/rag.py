@@ -109,6 +109,15 @@ class RAGPipeline:
         # from cached pieces split at paragraph boundaries (the byte-level BPE never merges
         # across a newline pre-token), so only the question is tokenised per request
         self._chunk_ids: dict[int, list[int]] = {}
+        # the owner of the (index, metadata) pair (SemanticIndexer / IndexFollower), handed over
+        # like its columns (services/stack.py).  Row ids are positions and a delete shifts them:
+        # ``owner.generation`` is odd while a delete swaps the pair and changes with every one,
+        # so :meth:`resolve` reads it before the search and again once ids are resolved to
+        # records and prompts, and redoes the batch's retrieval when it moved.  Deletes are
+        # rare: no lock on the hot path.  None: nobody deletes, nothing is checked
+        self.owner = None
+        self._generation = 0
+        self._after_search = None        # test hook: called between the search and the resolve
         self._pieces = None
         if hasattr(chat_tokenizer, "special") and template.count("{context}") == 1 \
                 and template.count("{question}") == 1 and template.index("{context}") < template.index("{question}"):
@@ -301,6 +310,69 @@ class RAGPipeline:
             self._host_ids(I)
         return D, I
 
+    def _new_generation(self, gen: int) -> None:
+        """Row ids changed meaning: everything cached by id goes, and columns this pipeline
+        built itself are rebuilt from the metadata list (an owner's are compacted by it)."""
+        self._chunk_ids.clear()
+        self._seen.clear()
+        if self._own_scopes is not None and self._own_scopes is self.scopes:
+            self.scopes.rebuild(self.metadata)
+        if self._own_lexical is not None and self._own_lexical is self.lexical:
+            self.lexical.rebuild(self.metadata)
+        self._generation = gen
+
+    def _resolve_ids(self, questions: list[str], I, span: str | None):
+        if span is None:
+            return self.build_prompts(questions, I), self._sources(I)
+        with tracing.span(span, n=len(questions)):
+            return self.build_prompts(questions, I), self._sources(I)
+
+    def _even_generation(self) -> int:
+        """The owner's generation once no delete is swapping.  The counter is odd only inside
+        the swap's critical section under the index lock, so an odd value is waited out on that
+        lock -- however long the swap takes, no retry is counted for it."""
+        owner = self.owner
+        g = owner.generation
+        while g & 1:
+            lock = getattr(self.index, "_lock", None)
+            if lock is not None:
+                with lock:
+                    pass
+            else:
+                time.sleep(0)
+            g = owner.generation
+        return g
+
+    def resolve(self, questions: list[str], search, span: str | None = None):
+        """One batch's retrieval, safe against a concurrent delete: ``search()`` -> the hits as
+        host id lists; -> (I, prompts, sources) with the ids resolved to prompts (inside the
+        tracing span ``span``, if any) and to each question's sources while they still name the rows the
+        search saw.  Without an owner this is search + :meth:`build_prompts` and nothing else."""
+        owner = self.owner
+        if owner is None:
+            I = search()
+            return (I, *self._resolve_ids(questions, I, span))
+        for _ in range(16):                   # one round per delete that lands inside a retrieval
+            g0 = self._even_generation()
+            if g0 != self._generation:
+                self._new_generation(g0)
+            try:
+                I = search()
+                if self._after_search is not None:
+                    self._after_search()
+                prompts, sources = self._resolve_ids(questions, I, span)
+            except (IndexError, KeyError):    # a list that shrank under the resolve
+                if owner.generation == g0:
+                    raise
+                continue
+            if owner.generation == g0:
+                return I, prompts, sources
+        raise RuntimeError("retrieval raced 16 deletes in a row")
+
+    def _sources(self, I: list[list[int]]) -> list[list]:
+        meta = self.metadata
+        return [[meta[i].get("source") for i in ids if 0 <= i < len(meta)] for ids in I]
+
     def _piece_prompt(self, qtext: str, ids: list[int], qids: list[int] | None = None) -> list[int]:
         ct = self.chat_tok
         if not hasattr(self, "_frame"):
@@ -390,12 +462,17 @@ class RAGPipeline:
             qemb = self.embed(questions)
             self._sync()
         t1 = time.perf_counter()
-        with tracing.span("rag.search", n=len(questions), k=self.k):
-            D, I = self.search(qemb, scopes, modes, questions, mmr)
-            I = self._host_ids(I)  # host needs ids to assemble the prompts
-        t2 = time.perf_counter()
-        with tracing.span("rag.prompt", n=len(questions)):
-            prompts = self.build_prompts(questions, I)
+        tm = {}
+
+        def hits():
+            with tracing.span("rag.search", n=len(questions), k=self.k):
+                D, I = self.search(qemb, scopes, modes, questions, mmr)
+                I = self._host_ids(I)  # host needs ids to assemble the prompts
+            tm["t2"] = time.perf_counter()
+            return I
+
+        I, prompts, sources = self.resolve(questions, hits, "rag.prompt")
+        t2 = tm["t2"]
         t3 = time.perf_counter()
         with tracing.span("rag.generate", n=len(prompts)):
             outs = self.engine.generate(prompts, params)
@@ -403,8 +480,7 @@ class RAGPipeline:
         t.embed_s, t.search_s, t.prompt_s, t.generate_s = t1 - t0, t2 - t1, t3 - t2, t4 - t3
         self.last_times = t
         res = []
-        for ids, toks in zip(I, outs):
-            srcs = [self.metadata[i].get("source") for i in ids if 0 <= i < len(self.metadata)]
+        for ids, toks, srcs in zip(I, outs, sources):
             res.append(Answer(answer=self.chat_tok.decode(toks), sources=srcs, token_ids=toks,
                               chunk_ids=list(ids)))
         return res
@@ -433,19 +509,27 @@ class RAGPipeline:
                 evs[0].record(stream)
                 qemb = self.embed(questions)
                 evs[1].record(stream)
-                _, I = self.search(qemb, scopes, mmr=mmr)
-                evs[2].record(stream)
-                I = self._host_ids(I)       # waits for this side stream only
-            host = None
         else:
             qemb = self.embed(questions)
             tm = time.perf_counter()
-            _, I = self.search(qemb, scopes, mmr=mmr)
-            I = self._host_ids(I)
-            host = (tm - t0, time.perf_counter() - tm)
-        t1 = time.perf_counter()
-        with tracing.span("rag.prompts", n=len(questions)):
-            prompts = self.build_prompts(questions, I)
+        stamp = {}
+
+        def hits():
+            if stream is not None:
+                with torch.cuda.stream(stream):
+                    _, I = self.search(qemb, scopes, mmr=mmr)
+                    if "t1" not in stamp:       # a retry after a delete is not timed again
+                        evs[2].record(stream)
+                    I = self._host_ids(I)       # waits for this side stream only
+            else:
+                _, I = self.search(qemb, scopes, mmr=mmr)
+                I = self._host_ids(I)
+            stamp.setdefault("t1", time.perf_counter())
+            return I
+
+        I, prompts, sources = self.resolve(questions, hits, "rag.prompts")
+        t1 = stamp["t1"]
+        host = None if stream is not None else (tm - t0, t1 - tm)
         reserved = None
         if params is not None and len(prompts) <= self.engine.max_batch:
             try:
@@ -455,7 +539,7 @@ class RAGPipeline:
                 # first and reserves this batch itself (reserved=None)
                 reserved = None
         sp.__exit__(None, None, None)
-        return questions, I, prompts, reserved, (evs, host), t0, t1, time.perf_counter()
+        return questions, I, prompts, reserved, (evs, host), t0, t1, time.perf_counter(), sources
 
     @torch.inference_mode()
     def answer_pipelined(self, batches: list[list[str]], params: SamplingParams | None = None,
@@ -497,7 +581,7 @@ class RAGPipeline:
         eng = self.engine
         cuda = eng.device.type == "cuda"
         stream = torch.cuda.Stream() if cuda else None
-        pending = None   # (Launched, questions, I, stage timers, t0, t1, t2, t3) of the batch in flight
+        pending = None   # (Launched, questions, I, sources, stage timers, t0, t1, t2, t3) of the batch in flight
 
         def stage_times(tm, t0, t1, t2, gen_s):
             evs, host = tm
@@ -508,7 +592,7 @@ class RAGPipeline:
             return StageTimes(embed_s=emb, search_s=srch, prompt_s=t2 - t1, generate_s=gen_s)
 
         def finish(p):
-            h, questions, I, tm, t0, t1, t2, t3 = p
+            h, questions, I, sources, tm, t0, t1, t2, t3 = p
             outs = eng.collect(h)
             t4 = time.perf_counter()
             if cuda:
@@ -521,9 +605,8 @@ class RAGPipeline:
             st = stage_times(tm, t0, t1, t2, gen_s)
             self.last_times = st
             with tracing.span("rag.detokenise", n=len(outs)):
-                res = [Answer(answer=self.chat_tok.decode(toks),
-                              sources=[self.metadata[j].get("source") for j in ids if 0 <= j < len(self.metadata)],
-                              token_ids=toks, chunk_ids=list(ids)) for ids, toks in zip(I, outs)]
+                res = [Answer(answer=self.chat_tok.decode(toks), sources=srcs,
+                              token_ids=toks, chunk_ids=list(ids)) for ids, toks, srcs in zip(I, outs, sources)]
             return res, st, latency
 
         # batch i-1 is collected and detokenised on a helper thread as soon as batch i's
@@ -538,7 +621,7 @@ class RAGPipeline:
             fin = None
             try:
                 for i in range(len(batches)):
-                    questions, I, prompts, reserved, tm, t0, t1, t2 = fut.result()
+                    questions, I, prompts, reserved, tm, t0, t1, t2, sources = fut.result()
                     fut = None
                     # preparation cost, not the wait for the gate: GPU embed + search time (side
                     # stream events, complete once the host has the hits) + host prompt assembly
@@ -583,16 +666,14 @@ class RAGPipeline:
                         f, fin = fin, None
                         yield f.result()
                     if h is not None:
-                        pending = (h, questions, I, tm, t0, t1, t2, t3)
+                        pending = (h, questions, I, sources, tm, t0, t1, t2, t3)
                     else:
                         t4 = time.perf_counter()
                         st = stage_times(tm, t0, t1, t2, t4 - t3)
                         self.last_times = st
-                        yield ([Answer(answer=self.chat_tok.decode(toks),
-                                       sources=[self.metadata[j].get("source") for j in ids
-                                                if 0 <= j < len(self.metadata)], token_ids=toks,
+                        yield ([Answer(answer=self.chat_tok.decode(toks), sources=srcs, token_ids=toks,
                                        chunk_ids=list(ids))
-                                for ids, toks in zip(I, outs)], st, t4 - t0)
+                                for ids, toks, srcs in zip(I, outs, sources)], st, t4 - t0)
                 if pending is not None:
                     p, pending = pending, None
                     yield finish(p)

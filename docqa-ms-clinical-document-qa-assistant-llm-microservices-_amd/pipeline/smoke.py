@@ -19,6 +19,19 @@ def run_smoke(device: str = "cuda", llm: str = "llama3-8b") -> dict:
     ans = pipe.answer_batch(qs, SamplingParams(max_new_tokens=4, stop_on_eos=False))
     assert len(ans) == 2 and all(len(a.sources) == 3 for a in ans)
     assert all(len(a.token_ids) == 4 for a in ans)
+    # add - delete - search: eight rows appended and removed again (the compaction kernels,
+    # csrc/kernels/compact.hip) leave every hit as it was
+    from ..index.flat import FlatIndex
+
+    idx = pipe.index
+    if isinstance(idx, FlatIndex):
+        n = idx.ntotal
+        probe = idx.xb[:2].float()
+        want = idx.search(probe, 3)
+        idx.add(idx.xb[:8].float() + 1.0)
+        assert idx.remove_ids(list(range(n, n + 8))) == 8 and idx.ntotal == n
+        got = idx.search(probe, 3)
+        assert torch.equal(got[1], want[1]) and torch.equal(got[0], want[0])
     if device != "cpu":
         torch.cuda.synchronize()
         assert ops.native_loaded(), "native kernels were not used"

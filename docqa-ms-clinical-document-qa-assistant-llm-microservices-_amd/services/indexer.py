@@ -19,6 +19,10 @@ HTTP (the endpoint the reference's synthese-comparative expects but nobody serve
 synthese-comparative/core/retrieval_client.py:72-91):
   GET  /api/search/patient-snippets?patient_id&from_date&to_date&focus -> [{doc_id, text}]
   POST /api/search {"query", "k"} -> hits;  GET /api/index/stats;  GET /health
+  DELETE /api/index/documents/{doc_id}, DELETE /api/index/patients/{patient_id}
+    -> {"removed", "ntotal", "version"}: the patient-file chunks of that document / patient leave
+    the index (FAISS remove_ids semantics: later row ids shift down; knowledge-base rows are
+    never deleted this way); 404 nothing matches, 422 a sharded store, 503 no index
     optional search_mode dense | lexical | hybrid (default RETRIEVAL_MODE): kNN, BM25 or their
     reciprocal rank fusion; "score" is the leg's own (L2 distance, BM25 score, RRF value)
     optional search_type similarity | mmr (default RETRIEVAL_SEARCH_TYPE) with lambda_mult in
@@ -42,14 +46,14 @@ from fastapi.responses import JSONResponse
 from ..bus.broker import get_broker
 from ..config import Settings, mmr_request
 from ..index import faiss_io
-from ..index.flat import FlatIndex  # noqa: F401  (the default store type)
+from ..index.flat import FlatIndex, removal_mask  # noqa: F401  (FlatIndex: the default store type)
 from ..index.hybrid import load_index, make_index
 from ..index.lexical import LexicalColumns, fetch_depth
 from ..index.scope import ScopeColumns, scope_request
 from ..pipeline.corpus import embed_records
 from ..schemas import SearchRequest
 from ..store import metadata_io
-from ..store.segment_log import SegmentLog, read_snapshot_marker, write_snapshot_marker
+from ..store.segment_log import DeleteFrame, SegmentLog, read_snapshot_marker, write_snapshot_marker
 from ..text.chunking import chunk_chars
 from ..text.dates import in_window, parse_date
 from ..utils import tracing
@@ -93,7 +97,7 @@ class PatientIndex:
 
 class SemanticIndexer:
     def __init__(self, encoder, tokenizer, settings: Settings | None = None, index: FlatIndex | None = None,
-                 metadata: list | None = None, device: str = "cuda", on_indexed=None):
+                 metadata: list | None = None, device: str = "cuda", on_indexed=None, on_deleted=None):
         self.st = settings or Settings()
         self.encoder = encoder
         self.tok = tokenizer
@@ -109,6 +113,11 @@ class SemanticIndexer:
         self.lexical: LexicalColumns | None = None
         self.lock = threading.RLock()
         self.on_indexed = on_indexed  # callback(doc_id) e.g. docs DB status -> INDEXED
+        self.on_deleted = on_deleted  # callback(doc_id) e.g. docs DB status -> DELETED
+        # a delete shifts row ids: odd while one is swapping the (index, metadata) pair, even
+        # otherwise, and bumped inside the swap's critical section.  Readers that resolve ids
+        # after a search without holding ``lock`` (pipeline/rag.py) compare it around their work
+        self.generation = 0
         self._ch = None
         self._depth = None          # broker queue-depth probe (group commit), None: per message
         self._pending: list = []
@@ -157,6 +166,11 @@ class SemanticIndexer:
             if self.wal is not None:   # batches made durable after the last snapshot
                 replayed = 0
                 for _, recs, vecs in self.wal.replay(after_seq=covered):
+                    if isinstance(recs, DeleteFrame):
+                        self._check_delete_frame(recs)
+                        self._apply_delete(recs["rows"])
+                        replayed += len(recs["rows"])
+                        continue
                     self.index.add(torch.from_numpy(vecs.copy()))
                     self.metadata.extend(recs)
                     self.patients.extend(self.metadata)
@@ -164,7 +178,7 @@ class SemanticIndexer:
                     self._lexical_extend()
                     replayed += len(recs)
                 if replayed:
-                    logger.info("replayed %d vectors from the write-ahead log", replayed)
+                    logger.info("replayed %d added / removed vectors from the write-ahead log", replayed)
                     self.version += 1
                     dirty = True
             if dirty:
@@ -242,6 +256,83 @@ class SemanticIndexer:
                 for c in chunk_chars(text or "", self.st.chunk_size)]
         return self.add_records(recs)
 
+    # ------------------------------------------------------------------ deletion
+    def delete_document(self, doc_id) -> int:
+        """Remove every chunk of the patient document ``doc_id``; returns the rows removed."""
+        return self._delete("doc_id", doc_id)
+
+    def delete_patient(self, patient_id) -> int:
+        """Remove every chunk of every document of ``patient_id`` (erasure on request)."""
+        return self._delete("patient_id", patient_id)
+
+    def _delete(self, field: str, key) -> int:
+        """FAISS ``remove_ids`` semantics (surviving rows keep their order, later ids shift
+        down) for the ``patient_file`` rows whose ``field`` is ``key``; knowledge-base rows are
+        never deleted this way.  No matching row: 0, nothing logged.  Otherwise, under the
+        writer lock: the WAL frame first (durable before visible), then vectors, metadata,
+        scope / lexical columns and the patient map swapped together under the index lock."""
+        key = str(key)
+        with self.lock:
+            if self.index is None:
+                return 0
+            meta = self.metadata
+            rows = sorted(i for i in set(self.patients.rows(key))
+                          if meta[i].get("type") == "patient_file" and str(meta[i].get(field)) == key)
+            if not rows:
+                return 0
+            if not getattr(self.index, "can_remove", True):
+                self.index.remove_ids(rows)                # a sharded store: raises NotImplementedError
+            if self.wal is not None:                       # durable before it is visible
+                self.wal.append_delete(field, [key], rows, self.index.ntotal)
+            self._apply_delete(rows)
+            self.version += 1
+            self.commit()
+        logger.info("deleted %s=%s (%d chunks)", field, key, len(rows))
+        return len(rows)
+
+    def _check_delete_frame(self, frame: DeleteFrame) -> None:
+        rows, field, keys = frame["rows"], frame["field"], set(frame["keys"])
+        n = self.index.ntotal
+        if frame["ntotal_before"] != n or len(self.metadata) != n:
+            raise RuntimeError(f"delete frame expects {frame['ntotal_before']} rows, the index holds {n} "
+                               f"({len(self.metadata)} records)")
+        for i in rows:
+            m = self.metadata[i] if 0 <= i < n else {}
+            if m.get("type") != "patient_file" or str(m.get(field)) not in keys:
+                raise RuntimeError(f"delete frame names row {i}, which does not carry {field} in {sorted(keys)}")
+
+    def _apply_delete(self, rows: list[int]) -> None:
+        """Rows ``rows`` (ascending, unique, valid) leave the index, the metadata list (in place:
+        the QA side shares the list object), the columns and the patient map in one swap."""
+        n = self.index.ntotal
+        keep, pos, removed = removal_mask(rows, n, self.index.device)
+        gone = [self.metadata[i] for i in rows]
+
+        if removed != len(rows):
+            raise RuntimeError("delete: the rows named are not unique rows of the index")
+
+        def swap():
+            # everything that can fail -- the checks, the new device buffers -- comes first and
+            # changes nothing; from the bump on there are only list surgery and reference swaps
+            commit_scopes = self.scopes.prepare_remove(keep, pos, n - removed)
+            commit_lexical = (self.lexical.prepare_remove(keep, pos, n - removed, gone)
+                              if self.lexical is not None else None)
+            self.generation += 1                           # odd: ids and records are changing
+            metadata_io.drop_rows(self.metadata, rows)
+            commit_scopes()
+            if commit_lexical is not None:
+                commit_lexical()
+            self.patients.rebuild(self.metadata)
+
+        def swapped():                                     # last statement under the index lock
+            self.generation += 1
+
+        try:
+            self.index.remove_ids(rows, before_swap=swap, after_swap=swapped, mask=(keep, pos, removed))
+        finally:
+            if self.generation & 1:                        # the swap itself failed half-way
+                self.generation += 1
+
     # ------------------------------------------------------------------ queue
     def callback(self, ch, method, properties, body):
         """Queue consumer (reference semantics: chunk, embed, persist, then ack).
@@ -256,11 +347,19 @@ class SemanticIndexer:
         if waiting > 0 and len(self._pending) < self.BATCH_DOCS:
             return
         batch, self._pending = self._pending, []
-        recs, done = [], []
+        recs, done, deleted = [], [], False
         for c, m, b in batch:
             try:
                 msg = json.loads(b)
                 doc_id = msg.get("doc_id")
+                if msg.get("op") == "delete":
+                    # order on the queue is order in the index: the adds collected so far first
+                    if done:
+                        self._flush_adds(recs, done)
+                        recs, done = [], []
+                    self._delete_message(c, m, doc_id)
+                    deleted = True
+                    continue
                 md = msg.get("metadata") or {}
                 recs.extend({"doc_id": str(doc_id), "text_content": chunk, "source": f"Dossier Patient {doc_id}",
                              "type": "patient_file", "patient_id": md.get("patient_id", str(doc_id)),
@@ -270,6 +369,10 @@ class SemanticIndexer:
             except Exception as e:  # noqa: BLE001 - malformed message: dead-letter it
                 logger.error("indexing error: %s", e)
                 c.basic_nack(delivery_tag=m.delivery_tag, requeue=False)
+        if done or not deleted:
+            self._flush_adds(recs, done)
+
+    def _flush_adds(self, recs: list, done: list) -> None:
         try:
             n = self.add_records(recs)
             self.commit()
@@ -283,6 +386,17 @@ class SemanticIndexer:
             if self.on_indexed is not None and isinstance(doc_id, int):
                 self.on_indexed(doc_id)
         logger.info("indexed %d doc(s) (%d chunks)", len(done), n)
+
+    def _delete_message(self, c, m, doc_id) -> None:
+        try:
+            self.delete_document(doc_id)
+        except Exception as e:  # noqa: BLE001
+            logger.error("delete error: %s", e)
+            c.basic_nack(delivery_tag=m.delivery_tag, requeue=False)
+            return
+        c.basic_ack(delivery_tag=m.delivery_tag)
+        if self.on_deleted is not None and isinstance(doc_id, int):
+            self.on_deleted(doc_id)
 
     BATCH_DOCS = 64
 
@@ -380,15 +494,17 @@ class SemanticIndexer:
         the ``focus`` text."""
         pid = str(patient_id)
         lo, hi = parse_date(from_date), parse_date(to_date)
+        # row ids are positions and a delete shifts them: the id list, the records and the
+        # vectors are read under ONE hold of the lock (the focus is embedded before it)
+        q = self.encoder.encode(self.tok.encode_batch([focus])) if focus else None
+        xb = None
         with self.lock:   # O(rows of this patient): the per-patient map, never a metadata scan
-            ids = self.patients.rows(pid)
             meta = self.metadata
-        rows = [(i, meta[i]) for i in ids if in_window(meta[i].get("note_date"), lo, hi)]
-        if focus and rows:
-            q = self.encoder.encode(self.tok.encode_batch([focus]))
-            ids = torch.tensor([i for i, _ in rows], device=self.index.xb.device)
-            with self.lock:
+            rows = [(i, meta[i]) for i in self.patients.rows(pid) if in_window(meta[i].get("note_date"), lo, hi)]
+            if q is not None and rows:
+                ids = torch.tensor([i for i, _ in rows], device=self.index.xb.device)
                 xb = self.index.xb.index_select(0, ids).float()
+        if xb is not None:
             d = ((xb - q.to(xb.device)) ** 2).sum(1)
             order = d.argsort().tolist()
             rows = [rows[j] for j in order]
@@ -435,6 +551,25 @@ def create_app(indexer: SemanticIndexer) -> FastAPI:
         if scope is None:
             return indexer.search(req.query, req.k)
         return indexer.search(req.query, req.k, scope)
+
+    def _delete(fn, key):
+        if indexer.index is None:
+            return JSONResponse(status_code=503, content={"detail": "Index non chargé."})
+        try:
+            removed = fn(key)
+        except NotImplementedError as e:
+            return JSONResponse(status_code=422, content={"detail": str(e)})
+        if not removed:
+            return JSONResponse(status_code=404, content={"detail": "No indexed chunk matches"})
+        return {"removed": removed, "ntotal": indexer.index.ntotal, "version": indexer.version}
+
+    @app.delete("/api/index/documents/{doc_id}")
+    def delete_document(doc_id: str):
+        return _delete(indexer.delete_document, doc_id)
+
+    @app.delete("/api/index/patients/{patient_id}")
+    def delete_patient(patient_id: str):
+        return _delete(indexer.delete_patient, patient_id)
 
     @app.get("/api/search/patient-snippets")
     def patient_snippets(patient_id: str, from_date: str | None = None, to_date: str | None = None,

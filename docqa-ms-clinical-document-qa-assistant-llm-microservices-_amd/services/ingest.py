@@ -8,6 +8,14 @@ Contract (doc-ingestor/main.py:19-74, processing.py:10-44):
                    status ERROR_QUEUE (kept for client compatibility)
   GET  /documents/ -> all rows {id, filename, upload_date, status, doc_type}
   GET  /documents/{id} -> one row (new: readiness polling instead of a blind sleep)
+  DELETE /documents/{id} (new) -> 404 unknown id; 409 while PENDING / PROCESSED (the document is
+                   still in the pipeline: its own indexing could overtake the delete); INDEXED:
+                   status DELETING, a ``{"op": "delete", "doc_id"}`` message goes on the clean
+                   queue, then the uploaded file is removed, 202 -- the indexer's ``on_deleted``
+                   hook sets DELETED; DELETING: the same again (the message is idempotent, so a
+                   delete the indexer dead-lettered can be retried); a failed publish is a 503 and
+                   leaves status and file as they were; ERROR_*: nothing was indexed, the
+                   file is removed and the status set to DELETED, 200; DELETED: 200
   GET  /health     -> {"status": "ok", "service": "doc-ingestor"}
 The raw_documents_queue message is ``{"doc_id", "text", "metadata": {"filename", "type"}}``
 (key order preserved), persistent, on a durable queue.  Routes are sync ``def`` so the
@@ -100,6 +108,39 @@ def create_app(settings: Settings | None = None, db: docs_db.DocsDB | None = Non
         if d is None:
             return JSONResponse(status_code=404, content={"detail": "Document not found"})
         return d
+
+    def _remove_upload(doc_id: int) -> None:
+        for p in upload_dir.glob(f"{doc_id}_*"):
+            try:
+                p.unlink()
+            except OSError:
+                pass
+
+    @app.delete("/documents/{doc_id}")
+    def delete_document(doc_id: int):
+        d = db.get(doc_id)
+        if d is None:
+            return JSONResponse(status_code=404, content={"detail": "Document not found"})
+        status = d["status"]
+        if status in (docs_db.STATUS_PENDING, docs_db.STATUS_PROCESSED):
+            return JSONResponse(status_code=409, content={"detail": f"Document is {status}: retry once it is INDEXED",
+                                                          "status": status})
+        if status == docs_db.STATUS_DELETED:
+            return {"doc_id": doc_id, "status": status}
+        if status not in (docs_db.STATUS_INDEXED, docs_db.STATUS_DELETING):   # ERROR_*: nothing was indexed
+            _remove_upload(doc_id)
+            db.set_status(doc_id, docs_db.STATUS_DELETED)
+            return {"doc_id": doc_id, "status": docs_db.STATUS_DELETED}
+        # DELETING again: an earlier delete message may have been dead-lettered by the indexer;
+        # the message is idempotent (deleting what is not indexed removes nothing and is acked)
+        db.set_status(doc_id, docs_db.STATUS_DELETING)
+        try:
+            broker.publish(st.clean_queue, json.dumps({"op": "delete", "doc_id": doc_id}).encode())
+        except Exception as e:  # noqa: BLE001 - nothing happened: the status and the file stay
+            db.set_status(doc_id, status)
+            return JSONResponse(status_code=503, content={"detail": str(e)})
+        _remove_upload(doc_id)                         # only once the delete is on its way
+        return JSONResponse(status_code=202, content={"doc_id": doc_id, "status": docs_db.STATUS_DELETING})
 
     @app.get("/health")
     def health():

@@ -312,21 +312,24 @@ class ContinuousBatcher:
             tp0 = time.perf_counter()
             qs, scopes, modes, mmr = _ask_parts(asks)
             qemb = pipe.embed(qs)
-            if mmr is not None:
-                _, I = pipe.search(qemb, scopes, modes, qs, mmr)
-            elif modes is not None:
-                _, I = pipe.search(qemb, scopes, modes, qs)
-            else:
-                _, I = pipe.index.search(qemb, pipe.k) if scopes is None else pipe.search(qemb, scopes)
-            I = pipe._host_ids(I)
-            prompts = pipe.build_prompts(qs, I)
+
+            def hits():
+                if mmr is not None:
+                    _, I = pipe.search(qemb, scopes, modes, qs, mmr)
+                elif modes is not None:
+                    _, I = pipe.search(qemb, scopes, modes, qs)
+                else:
+                    _, I = pipe.index.search(qemb, pipe.k) if scopes is None else pipe.search(qemb, scopes)
+                return pipe._host_ids(I)
+
+            # ids resolved to prompts and sources while they name the rows the search saw
+            I, prompts, sources = pipe.resolve(qs, hits)
             te = time.perf_counter()
             m = self.metrics
             m.observe("ask_batch_size", len(asks))
             m.observe("ask_prep_batch_s", te - tp0)          # embed + search + prompt assembly
-            for (_, _, f, t0), ids, p in zip(asks, I, prompts):
+            for (_, _, f, t0), srcs, p in zip(asks, sources, prompts):
                 m.observe("ask_queue_s", tp0 - t0)            # arrival -> its prep batch starts
-                srcs = [pipe.metadata[j].get("source") for j in ids if 0 <= j < len(pipe.metadata)]
 
                 def done(ef, f=f, t0=t0, srcs=srcs):
                     if ef.exception() is not None:

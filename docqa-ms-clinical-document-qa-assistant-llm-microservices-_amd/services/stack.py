@@ -127,7 +127,8 @@ class DocQAStack:
             db = self.db
             self.indexer = indexer_mod.SemanticIndexer(
                 self.encoder, self.enc_tok, self.st, device=dev,
-                on_indexed=lambda i: db.set_status(i, docs_db.STATUS_INDEXED)).startup()
+                on_indexed=lambda i: db.set_status(i, docs_db.STATUS_INDEXED),
+                on_deleted=lambda i: db.set_status(i, docs_db.STATUS_DELETED)).startup()
             if opts.preload_notes:
                 from ..pipeline.corpus import build_corpus
 
@@ -153,6 +154,7 @@ class DocQAStack:
             owner = self.indexer if self.indexer is not None else self.follower
             self.pipeline.scopes = owner.scopes
             self.pipeline.lexical_owner = owner      # builds the BM25 term columns on first use
+            self.pipeline.owner = owner              # its generation counter guards row ids across deletes
             self.qa_app = qa.create_app(self.pipeline, self.st, lockstep=opts.qa_lockstep,
                                         replicas=list(opts.qa_replicas) or None)
         if "ingest" in svc:

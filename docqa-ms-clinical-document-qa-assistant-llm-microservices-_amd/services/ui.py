@@ -3,7 +3,8 @@ reference's Streamlit app (clinical-ui/app.py:1-118): sidebar health probes
 (``GET {url}/health``, 2 s timeout), document upload to ``POST /ingest/`` with
 ``doc_type="compte-rendu"`` and readiness polling of ``GET /documents/{id}`` (instead of
 a fixed 5 s sleep), and a chat box posting ``{"question"}`` to ``/ask/`` that renders the
-answer and its sources.  The page proxies to the services through the UI server so the
+answer and its sources; ``DELETE /ui/documents/{id}`` proxies the ingestor's delete route.  The
+page proxies to the services through the UI server so the
 browser never needs CORS."""
 from __future__ import annotations
 
@@ -64,6 +65,12 @@ def create_app(ingest_url: str = "http://127.0.0.1:8000", qa_url: str = "http://
     async def doc(doc_id: int):
         async with httpx.AsyncClient(timeout=5.0) as c:
             r = await c.get(f"{ingest_url}/documents/{doc_id}")
+        return JSONResponse(status_code=r.status_code, content=r.json())
+
+    @app.delete("/ui/documents/{doc_id}")
+    async def delete_doc(doc_id: int):
+        async with httpx.AsyncClient(timeout=5.0) as c:
+            r = await c.delete(f"{ingest_url}/documents/{doc_id}")
         return JSONResponse(status_code=r.status_code, content=r.json())
 
     @app.post("/ui/ask")

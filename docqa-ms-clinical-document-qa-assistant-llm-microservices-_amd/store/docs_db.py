@@ -5,7 +5,8 @@ Schema identical to the reference's ``documents`` table (doc-ingestor/models.py:
 Status lifecycle: PENDING -> PROCESSED | ERROR_EXTRACTION | ERROR_QUEUE
 (doc-ingestor/main.py:28,44,54,63), extended with INDEXED once the semantic indexer has
 made the document searchable (the reference has no readiness signal: its UI sleeps 5 s,
-clinical-ui/app.py:55-58).
+clinical-ui/app.py:55-58), and with INDEXED -> DELETING -> DELETED for a document deleted
+through ``DELETE /documents/{id}`` (ERROR_* -> DELETED directly: nothing was indexed).
 
 Backend: ``DATABASE_URL`` (default SQLite file); ``DOCQA_DB=postgres`` builds the
 reference URL ``postgresql://admin:adminpassword@DB_HOST:DB_PORT/ingestion_db``
@@ -28,6 +29,8 @@ STATUS_PROCESSED = "PROCESSED"
 STATUS_ERROR_EXTRACTION = "ERROR_EXTRACTION"
 STATUS_ERROR_QUEUE = "ERROR_QUEUE"
 STATUS_INDEXED = "INDEXED"
+STATUS_DELETING = "DELETING"   # DELETE /documents/{id} accepted: the delete message is on the clean queue
+STATUS_DELETED = "DELETED"     # the indexer removed the document's chunks (or nothing had been indexed)
 
 
 class DocumentMetadata(Base):

@@ -10,6 +10,7 @@ files.  Writes are atomic.
 from __future__ import annotations
 
 import io
+import itertools
 import pickle
 from pathlib import Path
 
@@ -40,6 +41,31 @@ def dumps_metadata(rows: list[dict]) -> bytes:
         clean.append({k: (v if isinstance(v, (str, int, float, bool, type(None))) else str(v))
                       for k, v in r.items()})
     return pickle.dumps(clean, protocol=4)
+
+
+_MAX_RUNS = 64
+
+
+def drop_rows(metadata: list, rows: list[int]) -> None:
+    """Delete the rows ``rows`` (ascending, unique) from the metadata list IN PLACE -- the list
+    object is shared with the QA side -- as contiguous runs, from the highest row down, so every
+    slice delete moves only the rows behind it once per run, not once per row.  A scattered
+    delete (more than ``_MAX_RUNS`` runs: every slice delete would move the whole tail again,
+    quadratic in a large list) is one pass over the list instead, assigned back in place."""
+    runs = sum(1 for j in range(len(rows)) if j == 0 or rows[j] != rows[j - 1] + 1)
+    if runs > _MAX_RUNS:
+        mask = bytearray(b"\x01") * len(metadata)
+        for r in rows:
+            mask[r] = 0
+        metadata[:] = list(itertools.compress(metadata, mask))
+        return
+    end = len(rows)
+    while end > 0:
+        start = end - 1
+        while start > 0 and rows[start - 1] == rows[start] - 1:
+            start -= 1
+        del metadata[rows[start]:rows[end - 1] + 1]
+        end = start
 
 
 def write_metadata(path, rows: list[dict]) -> None:
